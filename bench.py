@@ -34,8 +34,16 @@ steps cycle over distinct x0 batches ("slots").  A round of S steps (slots
 replayed K // S times, the remainder from one-step graphs (--no-chain: one
 graph launch per step); the kernels recompute everything on every replay.
 
-Per-kernel device times: HIP events around a graph of R back-to-back launches
-of that kernel alone, on the stream the graph runs on.
+A plain run sets up, warms up, times the steps and prints the result line
+(metric, value, unit, ms_per_step, dtype, config ...).  --dump-outputs DIR
+then also writes what the last timed step computed (z, status, ... of its
+slot) as DIR/<name>.npy; the inputs are seeded, so two builds run with the
+same arguments can be compared array for array.  --full adds everything else
+to the line: the oracle spot check and status statistics of what was timed,
+the host round trip, the per-kernel rooflines and the CPU baseline.
+
+Per-kernel device times (--full): HIP events around a graph of R back-to-back
+launches of that kernel alone, on the stream the graph runs on.
 
 Multi-GPU (torchrun): each rank owns its own batch (weak scaling), with no
 collective on the solve path.  There is a barrier and a synchronize around
@@ -236,6 +244,9 @@ class Config2:
     def status(self):
         return self.ST
 
+    def outputs(self, s):
+        return {"z": (self.Z[s], 0), "status": (self.ST[s], 0)}
+
     def kernels(self, traffic):
         """Per-kernel device times and rooflines; returns (dominant, others)."""
         R = self.args.reps
@@ -350,6 +361,10 @@ class Config2Loop:
 
     def status(self):
         return self.ST
+
+    def outputs(self, s):
+        o = self.outs[s]
+        return {"xs": (o["xs"], 1), "us": (o["us"], 1), "status": (o["status"], 1)}
 
     def kernels(self, traffic):
         R = self.args.reps
@@ -472,6 +487,9 @@ class Config3:
 
     def status(self):
         return self.ST
+
+    def outputs(self, s):
+        return {"z": (self.Z[s], 0), "y": (self.Y, 0), "status": (self.ST[s], 0)}
 
     def kernels(self, traffic):
         """Per-kernel rooflines of the z-space path, every stage timed by the
@@ -599,6 +617,9 @@ class Config4:
     def status(self):
         return self.ST
 
+    def outputs(self, s):
+        return {"z": (self.Z[s], 0), "y": (self.Y, 0), "status": (self.ST[s], 0)}
+
     def kernels(self, traffic):
         R = self.args.reps
         bsz, n, m, nx = self.args.batch, self.n, self.m, self.nx
@@ -694,6 +715,9 @@ class Config5:
 
     def status(self):
         return self.ST
+
+    def outputs(self, s):
+        return {"z": (self.Z[s], 0), "status": (self.ST[s], 0)}
 
     def kernels(self, traffic):
         R = self.args.reps
@@ -809,6 +833,9 @@ class ConfigNLP:
 
     def status(self):
         return self.ST
+
+    def outputs(self, s):
+        return {"z": (self.Z[s], 0), "status": (self.ST[s], 0), "kkt": (self.KKT[s], 0)}
 
     def counted_units(self, steps):
         """NLP solves that reached the KKT tolerance (status OPTIMAL) in the
@@ -1000,6 +1027,11 @@ class ConfigLoop:
     def status(self):
         return self.ST
 
+    def outputs(self, s):
+        b = self.bufs[s]
+        return {k: (b[k], 1) for k in ("xs", "us", "success", "iters", "state_prediction",
+                                       "input_prediction")}
+
     def optimal_frac(self):
         """Fraction of the controller calls (instance x sample, all slots)
         that converged."""
@@ -1148,6 +1180,12 @@ def main():
     ap.add_argument("--traffic", default=None,
                     help="JSON with PMC-measured HBM bytes per launch {kernel: bytes} "
                          "(tools/prof_counters.sh); fills roofline.traffic")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the oracle check, the status statistics, "
+                         "the host round trip, the per-kernel rooflines and the CPU baseline "
+                         "(--check, --reps, --cpu-seconds, --no-cpu, --traffic apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
     C = CONFIGS[args.config]
     args.batch = args.batch or C.default_batch
@@ -1264,36 +1302,15 @@ def main():
     if args.gather and world > 1 and hasattr(wl, "Z"):
         gather = time_gather(wl, args, world, dev, backend)
 
-    # ---- correctness of what was timed: statuses + oracle spot check (rank 0)
-    st = wl.status()
-    code = batched.status_code(st)
-    opt_frac = float((code == 0).double().mean())
-    if hasattr(wl, "optimal_frac"):  # the loop: per controller call, not per episode
-        opt_frac = wl.optimal_frac()
-    iters = batched.status_iters(st).double()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl.outputs((args.steps - 1) % S), args.dump_outputs)
 
     out = None
     if rank == 0:
-        # PMC-measured HBM bytes per launch (tools/traffic.sh), committed under
-        # profiles/ per config; --traffic overrides
-        traffic = {}
-        tpath = args.traffic or os.path.join(ROOT, "profiles", f"traffic_cfg{args.config}.json")
-        if os.path.exists(tpath) and (args.traffic or args.batch == C.default_batch):
-            with open(tpath) as fh:
-                traffic = json.load(fh)  # measured at the config's default batch
-        err = wl.check()
-        e2e = host_roundtrip(wl, graphs, args)
-        dom, others, extra = wl.kernels(traffic)
-        cpu = None
-        if not args.no_cpu and world == 1:
-            cpu = wl.cpu_baseline(args.cpu_seconds)
         cfg = wl.workload()
         cfg.update({"batch_per_gpu": args.batch, "parallelism": f"dp{world}",
                     "graph": graphs is not None, "graph_steps": S if chain is not None else 1,
                     "config": args.config})
-        if dom is None:
-            dom = {"note": "no single dominant kernel: see the nlp config for the per-kernel "
-                           "rooflines of one SQP iteration"}
         out = {
             "metric": METRIC,
             "value": round(value, 1),
@@ -1308,25 +1325,84 @@ def main():
             "dtype": wl.dname,
             "data": "synthetic",
             "config": cfg,
-            "max_abs_u_err_vs_oracle": err,
-            "optimal_frac": opt_frac,
-            "status_hist": {int(k): int(v) for k, v in zip(*np.unique(code.cpu().numpy(), return_counts=True))},
-            "iters_mean": round(float(iters.mean()), 2),
-            "iters_max": int(iters.max()),
-            "roofline": dom,
-            "cpu_baseline": cpu,
         }
-        if e2e is not None:
-            out["host_roundtrip"] = e2e
-        if gather is not None:
-            out["gather"] = gather
         if units != 1:
             out["unit"] = "closed-loop MPC steps/s"
-        out.update(others)
-        out.update(extra)
+        if gather is not None:
+            out["gather"] = gather
+        if args.full:
+            out.update(full_report(wl, C, args, graphs, world))
         print(json.dumps(out), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()
+    return out
+
+
+def dump_outputs(arrays, path, limit=60_000_000):
+    """--dump-outputs: the arrays a caller of the timed path receives from its
+    last step, as path/<name>.npy in float64 (status words decoded into
+    `status`, the code, and `status_iters`).  Beyond `limit` bytes in all,
+    every array keeps the same fixed, seeded sample of the batch (its indices
+    in `sample_index`)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = dict(arrays)
+    if "status" in arrays:
+        st, ax = arrays["status"]
+        arrays["status"] = (batched.status_code(st), ax)
+        arrays["status_iters"] = (batched.status_iters(st), ax)
+    bsz = next(t.shape[ax] for t, ax in arrays.values())
+    per = sum(t.numel() // bsz for t, _ in arrays.values()) * 8
+    idx = None
+    if per * bsz > limit:
+        keep = max(1, limit // (per + 8))
+        idx = np.sort(np.random.default_rng(20261015).choice(bsz, size=keep, replace=False))
+        np.save(os.path.join(path, "sample_index.npy"), idx.astype(np.float64))
+        idx = torch.as_tensor(idx, device=next(iter(arrays.values()))[0].device)
+    for name, (t, ax) in arrays.items():
+        if idx is not None:
+            t = t.index_select(ax, idx)
+        np.save(os.path.join(path, f"{name}.npy"), t.double().cpu().numpy())
+
+
+def full_report(wl, C, args, graphs, world):
+    """--full: correctness of what was timed (statuses + oracle spot check)
+    and the measurements beside the headline figure -- host round trip,
+    per-kernel rooflines, CPU baseline -- as further keys of the result line."""
+    st = wl.status()
+    code = batched.status_code(st)
+    opt_frac = float((code == 0).double().mean())
+    if hasattr(wl, "optimal_frac"):  # the loop: per controller call, not per episode
+        opt_frac = wl.optimal_frac()
+    iters = batched.status_iters(st).double()
+    # PMC-measured HBM bytes per launch (tools/traffic.sh), committed under
+    # profiles/ per config; --traffic overrides
+    traffic = {}
+    tpath = args.traffic or os.path.join(ROOT, "profiles", f"traffic_cfg{args.config}.json")
+    if os.path.exists(tpath) and (args.traffic or args.batch == C.default_batch):
+        with open(tpath) as fh:
+            traffic = json.load(fh)  # measured at the config's default batch
+    err = wl.check()
+    e2e = host_roundtrip(wl, graphs, args)
+    dom, others, extra = wl.kernels(traffic)
+    cpu = None
+    if not args.no_cpu and world == 1:
+        cpu = wl.cpu_baseline(args.cpu_seconds)
+    if dom is None:
+        dom = {"note": "no single dominant kernel: see the nlp config for the per-kernel "
+                       "rooflines of one SQP iteration"}
+    out = {
+        "max_abs_u_err_vs_oracle": err,
+        "optimal_frac": opt_frac,
+        "status_hist": {int(k): int(v) for k, v in zip(*np.unique(code.cpu().numpy(), return_counts=True))},
+        "iters_mean": round(float(iters.mean()), 2),
+        "iters_max": int(iters.max()),
+        "roofline": dom,
+        "cpu_baseline": cpu,
+    }
+    if e2e is not None:
+        out["host_roundtrip"] = e2e
+    out.update(others)
+    out.update(extra)
     return out
 
 

@@ -53,7 +53,7 @@ def test_bench_gpus2_spawns_two_ranks(cfg, batch, n, es, tol):
     env.pop("WORLD_SIZE", None)
     extra = ["--config", cfg, "--batch", str(batch)] if cfg else []
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8",
-                        "--warmup", "2", "--no-cpu", "--check", "16"] + extra,
+                        "--warmup", "2", "--full", "--no-cpu", "--check", "16"] + extra,
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

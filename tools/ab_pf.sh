@@ -7,6 +7,6 @@ timeout -k 10 300 python -u -m pytest tests/test_gpu_qp.py tests/test_gpu_sweep.
 tail -1 $O/ab_pytest.log
 for c in 3 5; do timeout -k 10 120 python tools/phase_timing.py pf$c 2>/dev/null | tail -8 | sed "s/^/pf$c /"; done
 for c in 3 5; do
-  timeout -k 10 200 python bench.py --config $c --steps 20 --warmup 3 --no-cpu > $O/ab_cfg$c.json 2>$O/ab_cfg$c.err
+  timeout -k 10 200 python bench.py --config $c --steps 20 --warmup 3 --full --no-cpu > $O/ab_cfg$c.json 2>$O/ab_cfg$c.err
   python -c "import json; d=json.load(open('$O/ab_cfg$c.json')); print($c, d['value'], d['max_abs_u_err_vs_oracle'], d['status_hist'], d.get('kernel_us'))"
 done

@@ -11,7 +11,7 @@ for rep in 1 2; do
   for t in base "${TAGS[@]}"; do
     lib=$ROOT/model_predictive_control_amd/lib/libmpcqp.so
     [ "$t" != base ] && lib=$ROOT/model_predictive_control_amd/lib/variants/libmpcqp_$t.so
-    MPCQP_LIB=$lib timeout -k 10 300 python bench.py --config $CFG --no-cpu "$@" > $OUT/ab_${CFG}_${t}_$rep.json 2> $OUT/ab_${CFG}_${t}_$rep.err \
+    MPCQP_LIB=$lib timeout -k 10 300 python bench.py --config $CFG --full --no-cpu "$@" > $OUT/ab_${CFG}_${t}_$rep.json 2> $OUT/ab_${CFG}_${t}_$rep.err \
       || { echo "FAIL $t"; tail -5 $OUT/ab_${CFG}_${t}_$rep.err; exit 1; }
     python3 -c "
 import json,sys

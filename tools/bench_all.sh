@@ -6,7 +6,7 @@ OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd $ROOT
 for c in 2 3 4 5; do
-  timeout -k 10 400 python bench.py --config $c --steps ${STEPS:-20} --warmup 3 --cpu-seconds ${CPUS:-5} "$@" \
+  timeout -k 10 400 python bench.py --config $c --full --steps ${STEPS:-20} --warmup 3 --cpu-seconds ${CPUS:-5} "$@" \
       > $OUT/${TAG}_cfg$c.json 2> $OUT/${TAG}_cfg$c.err
   rc=$?
   echo "cfg$c rc=$rc"; cat $OUT/${TAG}_cfg$c.json | cut -c1-1500; tail -3 $OUT/${TAG}_cfg$c.err

@@ -17,7 +17,7 @@ echo "default:"; cut -c1-600 $OUT/${TAG}_default.json
 cd $ROOT
 for c in $CFGS; do
   [ "$c" = "2" ] && continue
-  timeout -k 10 500 python3 bench.py --config $c > $OUT/${TAG}_cfg$c.json 2> $OUT/${TAG}_cfg$c.err
+  timeout -k 10 500 python3 bench.py --config $c --full > $OUT/${TAG}_cfg$c.json 2> $OUT/${TAG}_cfg$c.err
   rc=$?
   echo "cfg$c rc=$rc"; cut -c1-900 $OUT/${TAG}_cfg$c.json; tail -2 $OUT/${TAG}_cfg$c.err
   if [ $rc -ne 0 ]; then exit $rc; fi
