@@ -4,8 +4,13 @@
 //   min  sum_{k<N} x_k'Q x_k + u_k'R u_k + x_N'Qf x_N        (main.py:86-106)
 //
 // i.e. MPCController.solve (session_4/main.py:115-116 / session4_sol.py:
-// 128-129) for the input-box OCP, one instance per wavefront, nothing but the
-// plant, x0 and the bounds read from HBM and only z written back.
+// 128-129) for the input-box OCP, nothing but the plant, x0 and the bounds read
+// from HBM and only z written back.  mpcqp_mpc_box runs mpc_group_kernel
+// (quad_box.hip: four instances per wavefront, -H^{-1} as a Gram product of
+// closed-loop rollouts) by default; this file holds the entry point and
+// mpc_box_kernel, one instance per wavefront (MPCQP_KERNEL=wave), which builds
+// -H^{-1} column by column as derived below and so checks the other
+// construction independently.
 //
 // The box active set (gi_box_core.hpp) starts from M = -H^{-1}.  Instead of
 // forming H and inverting it with n Gauss-Jordan sweeps, the kernel uses the

@@ -3,9 +3,27 @@
 // blocks.  Two kernels:
 //   box_quad_kernel  -- mpcqp_solve_box: packed H in, n sweeps form -H^{-1},
 //                       then the group-wise Goldfarb-Idnani active set;
-//   mpc_quad_kernel  -- mpcqp_mpc_box: per-instance plant in, Riccati-built
-//                       -H^{-1} (see mpc_box.hip for the derivation), same
-//                       active set; nothing but (A, B, x0, bounds) and z cross HBM.
+//   mpc_group_kernel -- mpcqp_mpc_box: per-instance plant in, same active set;
+//                       nothing but (A, B, x0, bounds) and z cross HBM.
+//
+// mpc_group_kernel builds M = -H^{-1} from one backward Riccati pass
+//     S_k = R + B_k'P_{k+1}B_k,  K_k = -S_k^{-1} B_k'P_{k+1}A_k,
+//     P_k = Q + A_k'P_{k+1}A_k + A_k'P_{k+1}B_k K_k,   P_N = Qf
+// without ever forming H:  H = T' diag(S_k) T with T: u -> (u_k - K_k x_k(u))
+// unit lower block triangular, so H^{-1} = W diag(S_k^{-1}) W' with W = T^{-1}
+// (mpc_factor.hpp).  In order:
+//   1. stage in: every global load of the group is issued before the first wait;
+//   2. Riccati stage N-1-t next to free-response (x-bar) stage t, one loop;
+//   3. every lane rolls its column(s) of W~ = W diag(chol(S_k^{-1})) forward in
+//      lockstep over the stages (closed loop from u_j = L_j[:, b]; K_k and
+//      A_k + B_k K_k are broadcast LDS reads), next to the backward adjoint
+//      y_k = Q xbar_k + A_k'y_{k+1} that yields f_k = B_k'y_{k+1};
+//   4. M = -W~ W~' accumulated from the LDS tile straight into the register
+//      blocks, bitwise symmetric;
+//   5. Goldfarb-Idnani on M (quad.hpp).
+// (mpc_box.hip, the one-QP-per-wave path, builds the columns of H^{-1} one by
+// one instead and serves as the independent comparator in the tests.)
+#include "mpc_factor.hpp"
 #include "quad.hpp"
 #include "quad_api.hpp"
 
@@ -105,7 +123,12 @@ __global__ __launch_bounds__(64, (QuadOcc<T, BS>::w)) void box_quad_kernel(BoxAr
 // ----------------------------------------------------------- fused kernel
 template <typename T, int NX, int NU, class Mat>
 struct QMpcLds {
-  int oA, oB, oQ, oQf, oR, oC, oX0, oK, oSi, oAcl, oX, oKf, oMinv, total, ld;
+  // oW: the W~ tile, column c at oW + c*ld, all Mat::NV rows written.  ld is
+  // odd, so the 16 lanes of a group, each storing one row of its own column
+  // (8-byte stores, 16 consecutive lanes per LDS cycle, 32 four-byte banks),
+  // hit 16 distinct bank pairs; the Gram product reads a lane's BS rows of one
+  // column contiguously (mpc_factor.hpp).
+  int oA, oB, oQ, oQf, oR, oC, oX0, oK, oSi, oAcl, oX, oW, total, ld;
   __host__ __device__ QMpcLds(int N, int n, int tv) {
     const int S = tv ? N : 1;
     oA = GBoxLds<Mat>::size;
@@ -119,10 +142,9 @@ struct QMpcLds {
     oSi = oK + N * NU * NX;
     oAcl = oSi + N * NU * NU;
     oX = oAcl + N * NX * NX;
-    oKf = oX + (N + 1) * NX;
-    oMinv = oKf + N * n * NU;
-    ld = n + 1;
-    total = (oMinv + n * ld + 1) & ~1;  // keep every group's base 16-byte aligned
+    oW = oX + (N + 1) * NX;
+    ld = Mat::NV + 1;
+    total = (oW + n * ld + 1) & ~1;  // keep every group's base 16-byte aligned
   }
 };
 
@@ -188,8 +210,7 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
   T* Sis = sm + L.oSi;
   T* Acls = sm + L.oAcl;
   T* Xs = sm + L.oX;
-  T* Kfs = sm + L.oKf;
-  T* Mv = sm + L.oMinv;
+  T* Wt = sm + L.oW;
   const int ld = L.ld;
 
 #ifdef MPCQP_PHASE_TIMING
@@ -198,46 +219,84 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
   // ------------------------------------------------------------- stage in
   bool nonfinite = false, badbox = false;
   {
+    // Element e of each array goes to lane e % GL.  The first element per
+    // lane of every array (all of them unless the plant is time-varying or
+    // there is a drift) and the bounds are loaded into registers before
+    // anything is stored, so the wave waits for about one HBM round trip
+    // instead of one per array.
+    static_assert(NX * NX <= GL && NU * NU <= GL, "one element per lane for Q, Qf, R");
+    constexpr int NB = (NV + GL - 1) / GL;
     const T* Ab = a.A + (int64_t)bl * a.sA;
-    for (int e = q; e < S * NX * NX; e += GL) {
+    const T* Bb = a.B + (int64_t)bl * a.sB;
+    const T* Cb = (live && a.c) ? a.c + (int64_t)b * a.sC : nullptr;
+    auto ldA = [&](int e) {
       const int s = e / (NX * NX), r = (e / NX) % NX, cc = e % NX;
-      const T v = (r < nx && cc < nx) ? Ab[(int64_t)s * nx * nx + r * nx + cc] : T(0);
+      return (r < nx && cc < nx) ? Ab[(int64_t)s * nx * nx + r * nx + cc] : T(0);
+    };
+    auto ldB = [&](int e) {
+      const int s = e / (NX * NU), r = (e / NU) % NX, cc = e % NU;
+      return (r < nx && cc < nu) ? Bb[(int64_t)s * nx * nu + r * nu + cc] : T(0);
+    };
+    auto ldC = [&](int e) {
+      const int k = e / NX, cc = e % NX;
+      return (Cb && cc < nx) ? Cb[k * nx + cc] : T(0);
+    };
+    const int rq = q / NX, cq = q % NX;
+    const bool inq = live && q < NX * NX && rq < nx && cq < nx;
+    const int ru = q / NU, cu = q % NU;
+    const T vA = (q < S * NX * NX) ? ldA(q) : T(0);
+    const T vB = (q < S * NX * NU) ? ldB(q) : T(0);
+    const T vQ = inq ? a.Q[(int64_t)b * a.sQ + rq * nx + cq] : T(0);
+    const T vQf = inq ? a.Qf[(int64_t)b * a.sQf + rq * nx + cq] : T(0);
+    // padded inputs get R = I so that S_k stays invertible (their B cols are 0)
+    const T vR = (live && ru < nu && cu < nu) ? a.R[(int64_t)b * a.sR + ru * nu + cu]
+                                               : (ru == cu ? T(1) : T(0));
+    const T vC = (q < N * NX) ? ldC(q) : T(0);
+    const T vX0 = (live && a.x0 && q < nx) ? a.x0[(int64_t)b * a.sX0 + q] : T(0);
+    T vlb[NB], vub[NB];
+#pragma unroll
+    for (int t = 0; t < NB; ++t) {
+      const int i = q + t * GL;
+      const bool v = live && i < n;
+      vlb[t] = (v && a.lb) ? a.lb[(int64_t)b * a.slb + i] : -Lim<T>::inf();
+      vub[t] = (v && a.ub) ? a.ub[(int64_t)b * a.sub + i] : Lim<T>::inf();
+    }
+    if (q < S * NX * NX) As[q] = vA;
+    if (q < S * NX * NU) Bs[q] = vB;
+    nonfinite |= !finite(vA) || !finite(vB);
+    if (q < NX * NX) {
+      Qs[q] = vQ;
+      Qfs[q] = vQf;
+    }
+    if (q < NU * NU) Rs[q] = vR;
+    if (q < N * NX) Cs[q] = vC;
+    if (q < NX) X0s[q] = vX0;
+#pragma unroll
+    for (int t = 0; t < NB; ++t) {
+      const int i = q + t * GL;
+      if (i < NV) {
+        const bool v = live && i < n;
+        lbs[i] = vlb[t];
+        ubs[i] = vub[t];
+        fs[i] = T(0);
+        badbox |= v && (!(vlb[t] <= vub[t]) || vlb[t] == Lim<T>::inf() || vub[t] == -Lim<T>::inf());
+      }
+    }
+    // the rest of a time-varying plant and of the drift
+#pragma unroll 4
+    for (int e = q + GL; e < S * NX * NX; e += GL) {
+      const T v = ldA(e);
       As[e] = v;
       nonfinite |= !finite(v);
     }
-    const T* Bb = a.B + (int64_t)bl * a.sB;
-    for (int e = q; e < S * NX * NU; e += GL) {
-      const int s = e / (NX * NU), r = (e / NU) % NX, cc = e % NU;
-      const T v = (r < nx && cc < nu) ? Bb[(int64_t)s * nx * nu + r * nu + cc] : T(0);
+#pragma unroll 4
+    for (int e = q + GL; e < S * NX * NU; e += GL) {
+      const T v = ldB(e);
       Bs[e] = v;
       nonfinite |= !finite(v);
     }
-    for (int e = q; e < NX * NX; e += GL) {
-      const int r = e / NX, cc = e % NX;
-      const bool in = live && r < nx && cc < nx;
-      Qs[e] = in ? a.Q[(int64_t)b * a.sQ + r * nx + cc] : T(0);
-      Qfs[e] = in ? a.Qf[(int64_t)b * a.sQf + r * nx + cc] : T(0);
-    }
-    for (int e = q; e < NU * NU; e += GL) {
-      const int r = e / NU, cc = e % NU;
-      // padded inputs get R = I so that S_k stays invertible (their B cols are 0)
-      Rs[e] = (live && r < nu && cc < nu) ? a.R[(int64_t)b * a.sR + r * nu + cc] : (r == cc ? T(1) : T(0));
-    }
-    const T* Cb = (live && a.c) ? a.c + (int64_t)b * a.sC : nullptr;
-    for (int e = q; e < N * NX; e += GL) {
-      const int k = e / NX, cc = e % NX;
-      Cs[e] = (Cb && cc < nx) ? Cb[k * nx + cc] : T(0);
-    }
-    if (q < NX) X0s[q] = (live && a.x0 && q < nx) ? a.x0[(int64_t)b * a.sX0 + q] : T(0);
-    for (int i = q; i < NV; i += GL) {
-      const bool v = live && i < n;
-      const T li = (v && a.lb) ? a.lb[(int64_t)b * a.slb + i] : -Lim<T>::inf();
-      const T ui = (v && a.ub) ? a.ub[(int64_t)b * a.sub + i] : Lim<T>::inf();
-      lbs[i] = li;
-      ubs[i] = ui;
-      fs[i] = T(0);
-      badbox |= v && (!(li <= ui) || li == Lim<T>::inf() || ui == -Lim<T>::inf());
-    }
+#pragma unroll 4
+    for (int e = q + GL; e < N * NX; e += GL) Cs[e] = ldC(e);
   }
   __syncthreads();
 
@@ -394,9 +453,34 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
     if (!ok) code = MPCQP_STATUS_NOT_CONVEX;
 
     MPCQP_PHASE(1);
-    // ---- adjoint y -> f (backward); x_k of the next stage is read from LDS
-    // one iteration ahead so the read overlaps this stage's FMA chain
+    // ---- columns of W~ (forward, lockstep) next to the adjoint y -> f
+    // (backward).  Lane q rolls column c = q (and c = q + GL when n > GL) of
+    // W~ (mpc_factor.hpp): with v_t = L_j[:, b] at the column's own stage
+    // t = j and 0 elsewhere,
+    //     u_t = K_t x_t + v_t,   x_{t+1} = (A_t + B_t K_t) x_t + B_t v_t,
+    // which is 0 before stage j, the start at j and the closed loop after it.
+    // Every lane is at the same stage, so Ks, Acls and Bs are broadcast reads.
+    // The adjoint is group-uniform and independent of the rollouts: stage
+    // N-1-t runs next to rollout stage t so that the two chains overlap; its
+    // x_k of the next stage is read from LDS one iteration ahead.
     __syncthreads();
+    constexpr int NCH = (NV + GL - 1) / GL;  // columns per lane
+    bool cv[NCH];
+    int cj[NCH];
+    T lj[NCH][NU], wx[NCH][NX];
+    T* Wc[NCH];
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+      const int c = q + ch * GL;
+      cv[ch] = c < n;
+      const int cc = cv[ch] ? c : 0;
+      const int jj = cc / nu;
+      cj[ch] = cv[ch] ? jj : -1;
+      chol_col<T, NU>(Sis + jj * NU * NU, cc - jj * nu, lj[ch]);
+      Wc[ch] = Wt + cc * ld;
+#pragma unroll
+      for (int qq = 0; qq < NX; ++qq) wx[ch][qq] = T(0);
+    }
     T yk[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
@@ -408,119 +492,114 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
     T xnext[NX];
 #pragma unroll
     for (int qq = 0; qq < NX; ++qq) xnext[qq] = Xs[(N - 1) * NX + qq];
-    for (int k = N - 1; k >= 0; --k) {
-      // f_(k,u) = B_k[:,u]' y_{k+1}
-      const T* Bk = Bs + (tv ? k : 0) * NX * NU;
-      if (q == 0) {
-        for (int u = 0; u < nu; ++u) {
-          T s = T(0);
+    // B of the rollout stage (Br) and of the adjoint stage (Ba) and A of the
+    // adjoint stage (Ar) stay in registers for the whole loop unless the
+    // plant is time-varying.  Every LDS read of an iteration is issued at its
+    // top, before its stores (which the compiler must assume alias them);
+    // K, A + B K and x-bar are read one stage ahead, after the time-varying
+    // reads so that a counted wait for those leaves them in flight.  With an
+    // invariant plant no stage waits for a read it has just issued.
+    T Ba[NX][NU], Kt[NU][NX], Act[NX][NX];
+    load_sq<T, NX, NU>(Bs, Br, NU);
+    load_sq<T, NX, NU>(Bs, Ba, NU);
+    load_sq<T, NU, NX>(Ks, Kt, NX);
+    load_sq<T, NX, NX>(Acls, Act, NX);
+    for (int t = 0; t < N; ++t) {
+      const int k = N - 1 - t;  // adjoint stage
+      if (tv) {
+        load_sq<T, NX, NU>(Bs + t * NX * NU, Br, NU);
+        load_sq<T, NX, NU>(Bs + k * NX * NU, Ba, NU);
+        load_sq<T, NX, NX>(As + k * NX * NX, Ar, NX);
+      }
+      const int tn = t + 1 < N ? t + 1 : t;
+      T Kn[NU][NX], Acn[NX][NX], xnn[NX];
+      load_sq<T, NU, NX>(Ks + tn * NU * NX, Kn, NX);
+      load_sq<T, NX, NX>(Acls + tn * NX * NX, Acn, NX);
 #pragma unroll
-          for (int qq = 0; qq < NX; ++qq) s = fma(Bk[qq * NU + u], yk[qq], s);
-          fs[k * nu + u] = s;
+      for (int qq = 0; qq < NX; ++qq) xnn[qq] = Xs[(k > 1 ? k - 1 : 1) * NX + qq];
+      {  // rollout stage t
+#pragma unroll
+        for (int ch = 0; ch < NCH; ++ch) {
+          const bool at = t == cj[ch];
+          T v[NU], u[NU], xn[NX];
+#pragma unroll
+          for (int i = 0; i < NU; ++i) {
+            v[i] = at ? lj[ch][i] : T(0);
+            T s = v[i];
+#pragma unroll
+            for (int qq = 0; qq < NX; ++qq) s = fma(Kt[i][qq], wx[ch][qq], s);
+            u[i] = s;
+          }
+#pragma unroll
+          for (int i = 0; i < NX; ++i) {
+            T s = T(0);
+#pragma unroll
+            for (int qq = 0; qq < NX; ++qq) s = fma(Act[i][qq], wx[ch][qq], s);
+#pragma unroll
+            for (int qq = 0; qq < NU; ++qq) s = fma(Br[i][qq], v[qq], s);
+            xn[i] = s;
+          }
+#pragma unroll
+          for (int qq = 0; qq < NX; ++qq) wx[ch][qq] = xn[qq];
+          // every row is written, the zeros before stage j included
+          if (cv[ch]) {
+#pragma unroll
+            for (int i = 0; i < NU; ++i)
+              if (i < nu) Wc[ch][t * nu + i] = u[i];
+          }
         }
       }
-      if (k == 0) break;
-      T xc[NX];
+      // adjoint stage k: f_(k,u) = B_k[:,u]' y_{k+1}, then y_k
+      if (q == 0) {
 #pragma unroll
-      for (int qq = 0; qq < NX; ++qq) {
-        xc[qq] = xnext[qq];
-        xnext[qq] = Xs[(k > 1 ? k - 1 : 1) * NX + qq];
+        for (int u = 0; u < NU; ++u) {
+          T s = T(0);
+#pragma unroll
+          for (int qq = 0; qq < NX; ++qq) s = fma(Ba[qq][u], yk[qq], s);
+          if (u < nu) fs[k * nu + u] = s;
+        }
       }
-      if (tv) load_sq<T, NX, NX>(As + k * NX * NX, Ar, NX);
-      T yn[NX];
+      if (k > 0) {
+        T yn[NX];
 #pragma unroll
-      for (int i = 0; i < NX; ++i) {
-        T s = T(0);
+        for (int i = 0; i < NX; ++i) {
+          T s = T(0);
 #pragma unroll
-        for (int qq = 0; qq < NX; ++qq) s = fma(Qr[i][qq], xc[qq], s);
+          for (int qq = 0; qq < NX; ++qq) s = fma(Qr[i][qq], xnext[qq], s);
 #pragma unroll
-        for (int qq = 0; qq < NX; ++qq) s = fma(Ar[qq][i], yk[qq], s);
-        yn[i] = s;
+          for (int qq = 0; qq < NX; ++qq) s = fma(Ar[qq][i], yk[qq], s);
+          yn[i] = s;
+        }
+#pragma unroll
+        for (int qq = 0; qq < NX; ++qq) yk[qq] = yn[qq];
       }
+      // next stage's operands
 #pragma unroll
-      for (int qq = 0; qq < NX; ++qq) yk[qq] = yn[qq];
+      for (int i = 0; i < NU; ++i)
+#pragma unroll
+        for (int qq = 0; qq < NX; ++qq) Kt[i][qq] = Kn[i][qq];
+#pragma unroll
+      for (int i = 0; i < NX; ++i)
+#pragma unroll
+        for (int qq = 0; qq < NX; ++qq) Act[i][qq] = Acn[i][qq];
+#pragma unroll
+      for (int qq = 0; qq < NX; ++qq) xnext[qq] = xnn[qq];
     }
+    // rows n .. NV-1 of the lane's columns: the padding of the register layout
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch)
+      if (cv[ch])
+        for (int i = n; i < NV; ++i) Wc[ch][i] = T(0);
   }
   __syncthreads();
 
   MPCQP_PHASE(2);
-  // ------------------------------ columns of -H^{-1}, one lane per column
-  for (int c = q; c < n; c += GL) {
-    const int jj = c / nu, bb = c - jj * nu;
-    T s[NX], kf[NU];
-    // k = jj: kff = S^{-1} e_b, s = -K' e_b
-#pragma unroll
-    for (int u = 0; u < NU; ++u) kf[u] = Sis[(jj * NU + u) * NU + bb];
-#pragma unroll
-    for (int qq = 0; qq < NX; ++qq) s[qq] = -Ks[(jj * NU + bb) * NX + qq];
-#pragma unroll
-    for (int u = 0; u < NU; ++u) Kfs[(jj * n + c) * NU + u] = kf[u];
-    for (int k = jj - 1; k >= 0; --k) {
-      const T* Bk = Bs + (tv ? k : 0) * NX * NU;
-      T t[NU];
-#pragma unroll
-      for (int u = 0; u < NU; ++u) {
-        T v = T(0);
-#pragma unroll
-        for (int qq = 0; qq < NX; ++qq) v = fma(Bk[qq * NU + u], s[qq], v);
-        t[u] = v;
-      }
-#pragma unroll
-      for (int u = 0; u < NU; ++u) {
-        T v = T(0);
-#pragma unroll
-        for (int qq = 0; qq < NU; ++qq) v = fma(Sis[(k * NU + u) * NU + qq], t[qq], v);
-        kf[u] = -v;
-        Kfs[(k * n + c) * NU + u] = kf[u];
-      }
-      T sn[NX];
-#pragma unroll
-      for (int i = 0; i < NX; ++i) {
-        T v = T(0);
-#pragma unroll
-        for (int qq = 0; qq < NX; ++qq) v = fma(Acls[(k * NX + qq) * NX + i], s[qq], v);
-        sn[i] = v;
-      }
-#pragma unroll
-      for (int qq = 0; qq < NX; ++qq) s[qq] = sn[qq];
-    }
-    // forward rollout from x_0 = 0
-    T x[NX];
-#pragma unroll
-    for (int qq = 0; qq < NX; ++qq) x[qq] = T(0);
-    for (int k = 0; k < N; ++k) {
-      const T* Ak = As + (tv ? k : 0) * NX * NX;
-      const T* Bk = Bs + (tv ? k : 0) * NX * NU;
-      T u[NU];
-#pragma unroll
-      for (int i = 0; i < NU; ++i) {
-        T v = (k <= jj) ? Kfs[(k * n + c) * NU + i] : T(0);
-#pragma unroll
-        for (int qq = 0; qq < NX; ++qq) v = fma(Ks[(k * NU + i) * NX + qq], x[qq], v);
-        u[i] = v;
-      }
-      for (int i = 0; i < nu; ++i) Mv[(k * nu + i) * ld + c] = -u[i];
-      T xn[NX];
-#pragma unroll
-      for (int i = 0; i < NX; ++i) {
-        T v = T(0);
-#pragma unroll
-        for (int qq = 0; qq < NX; ++qq) v = fma(Ak[i * NX + qq], x[qq], v);
-#pragma unroll
-        for (int qq = 0; qq < NU; ++qq) v = fma(Bk[i * NU + qq], u[qq], v);
-        xn[i] = v;
-      }
-#pragma unroll
-      for (int qq = 0; qq < NX; ++qq) x[qq] = xn[qq];
-    }
-  }
-  __syncthreads();
-
-  MPCQP_PHASE(3);
-  // ------------------------------------------------ box QP on M = -H^{-1}
+  // ------------------------------------------------ M = -W~ W~' = -H^{-1}
   Mat M;
   M.init(lane);
-  M.load_dense_sym(Mv, ld, n);
+  neg_gram<T>(M, Wt, ld, n);
+  MPCQP_PHASE(3);
+  // ---------------------------------------------------------- box QP on M
   for (int i = q; i < n; i += GL) nonfinite |= !finite(fs[i]);
   const unsigned long long gmask = (GL == 64 ? ~0ull : ((1ull << GL) - 1)) << (GL * g);
   if ((__ballot(nonfinite) & gmask) != 0) code = MPCQP_STATUS_NONFINITE;
