@@ -561,6 +561,14 @@ int mpcqp_sqp_shift(int dtype, int batch, int N, void* U, void* y, void* pi, int
  * input_prediction of ControllerLog), status (steps x batch; bits 8..23 =
  * sweeps + active-set iterations of the step; us and status may be NULL
  * when steps = 0).  Limits: nx <= 4, nu <= 2, N*nu <= 32.
+ * Status codes of a step (bits 0..7): OPTIMAL; MAXITER (z is the clipped
+ * iterate, the loop goes on from it); NOT_CONVEX (a pivot of H <= 0);
+ * INFEASIBLE (lb > ub); NONFINITE (NaN/Inf in H or F, or in the state x_t,
+ * i.e. from x0, A or B); NONFINITE goes before INFEASIBLE before NOT_CONVEX.  A step
+ * that ends in one of the last three writes NaN to us, zs and hence to
+ * x_{t+1}: the non-finite state poisons the rest of that instance's episode
+ * only (every later step repeats the code of the first failed one); the
+ * other instances, those of the same wavefront included, are not affected.
  */
 int mpcqp_mpc_box_loop(int dtype, int batch, int nx, int nu, int N, int steps,
                        const void* H, int64_t strideH, const void* F, int64_t strideF,

@@ -122,6 +122,7 @@ __global__ __launch_bounds__(64, (LoopOcc<T, BS>::w)) void box_loop_kernel(LoopA
   }
   __syncthreads();
   for (int e = q; e < P; e += 16) nonfinite |= live && !finite(Ps[e]);
+  for (int e = q; e < NMAX * NX; e += 16) nonfinite |= live && !finite(Fs[e]);
   const unsigned long long gmask = 0xFFFFull << (16 * g);
   const int code0 = ((__ballot(nonfinite) & gmask) != 0)
                         ? MPCQP_STATUS_NONFINITE
@@ -136,10 +137,29 @@ __global__ __launch_bounds__(64, (LoopOcc<T, BS>::w)) void box_loop_kernel(LoopA
   int st[BS];
 #pragma unroll
   for (int r = 0; r < BS; ++r) st[r] = (M.bi * BS + r < n) ? 0 : 3;  // cold first step
+  int failed = MPCQP_STATUS_OPTIMAL;  // code of the group's first failed step
+  // The states this lane's rows may take from the shift: bit 0 = the lower
+  // bound is finite (state 1), bit 1 = the upper one (state 2).  The bounds may
+  // differ along the horizon, and a row put on an infinite bound makes z
+  // infinite (two such rows: NaN multipliers that the release phase cannot
+  // order).
+  int okst[BS];
+#pragma unroll
+  for (int r = 0; r < BS; ++r) {
+    const int i = M.bi * BS + r;
+    okst[r] = (lbs[i] > -Lim<T>::inf() ? 1 : 0) | (ubs[i] < Lim<T>::inf() ? 2 : 0);
+  }
 
   for (int t = 0; t < a.steps; ++t) {
     // record x_t; f = F x_t (rows q, q + 16 of the group)
     if (live && q < nx) a.xs[((int64_t)t * a.batch + b) * nx + q] = xg[q];
+    // A NaN/Inf in x_t (from x0, A, B or a failed step; H and F are checked at
+    // stage-in) makes f non-finite: every violation is then NaN, the group
+    // "settles" and the final clamp turns the NaN z into a bound.  Every lane
+    // of the group reads the same x_t, so the flag needs no ballot.
+    bool nfx = false;
+#pragma unroll
+    for (int j = 0; j < NX; ++j) nfx |= !finite(xg[j]);
     for (int i = q; i < NMAX; i += 16) {
       T s = T(0);
 #pragma unroll
@@ -159,7 +179,12 @@ __global__ __launch_bounds__(64, (LoopOcc<T, BS>::w)) void box_loop_kernel(LoopA
       for (int bb = 0; bb < 4; ++bb)
         if ((bal >> (16 * g + 4 * bb)) & 1ull) fmask |= 1u << (bb * BS + r);
     }
-    int code = code0;
+    // NONFINITE goes before INFEASIBLE (code0 holds either), as in box_quad_kernel;
+    // the step then skips gi_box_st, writes NaN and leaves the next one cold.
+    // A failed step makes x NaN for the rest of the episode, whose steps
+    // repeat the code of that first failure (its cause), not NONFINITE.
+    int code = nfx ? MPCQP_STATUS_NONFINITE : code0;
+    if (failed != MPCQP_STATUS_OPTIMAL) code = failed;
     int sweeps = 0;
     bool okp = true;
     while (__any(fmask != 0)) {
@@ -183,6 +208,7 @@ __global__ __launch_bounds__(64, (LoopOcc<T, BS>::w)) void box_loop_kernel(LoopA
     if (code == MPCQP_STATUS_OPTIMAL) code = c2;
     const bool okc = code == MPCQP_STATUS_OPTIMAL || code == MPCQP_STATUS_MAXITER;
     if (!okc) {
+      failed = code;
 #pragma unroll
       for (int r = 0; r < BS; ++r) zr[r] = __builtin_nan("");
     }
@@ -214,7 +240,8 @@ __global__ __launch_bounds__(64, (LoopOcc<T, BS>::w)) void box_loop_kernel(LoopA
     for (int r = 0; r < BS; ++r) {
       const int i = M.bi * BS + r;
       const int src = i + nu < n ? i + nu : i;
-      st[r] = i < n ? (okc ? (int)sg[src] : 0) : 3;
+      const int s = okc ? ((int)sg[src] & okst[r]) : 0;  // states are 0, 1, 2
+      st[r] = i < n ? s : 3;
     }
     lds_exchange();
     if (q < NX) xg[q] = xn;

@@ -152,3 +152,343 @@ def test_lti_loop_helper(dev):
     assert out["success"].all()
     assert tuple(out["input_prediction"].shape) == (6, 2, 20, 1)
     assert torch.equal(out["input_prediction"][:, :, 0], out["us"])
+
+
+# ---------------------------------------------------------------------------
+# The loop off the easy path: every (NX, NU) x BS instantiation of
+# box_loop_kernel, bounds that differ along the horizon (so that the shifted
+# warm start is often wrong), one-sided and absent bounds, status codes, a
+# small max_iter and fp32.  Every episode is checked step by step at the
+# device's own recorded states (_check_episode), so that one differing step
+# cannot hide behind the divergence of two trajectories.
+# ---------------------------------------------------------------------------
+EPS32 = float(np.finfo(np.float32).eps)
+
+
+def _tol32(H):
+    """Relative fp32 tolerance on z (tests/test_gpu_mpc_box_edges.py):
+    max(2e-4, 3 * eps32 * cond(H)) with cond(H) <= 1e4."""
+    cond = np.linalg.cond(H)
+    assert cond <= 1e4, cond
+    return max(2e-4, 3 * EPS32 * cond)
+
+
+def _bnd(v, i, n):
+    """Bounds of instance i as an (n,) vector, or None."""
+    if v is None:
+        return None
+    v = np.asarray(v, float)
+    return np.broadcast_to(v[i] if v.ndim == 2 else v, (n,))
+
+
+def _check_episode(A, B, H, F, lb, ub, xs, us, zs, i, fp32=False, z_steps=None):
+    """Instance i of a device episode (xs (T+1, b, nx), us (T, b, nu), zs
+    (T, b, n) as float64 arrays) against the oracle at the device's own
+    states.  For every step t:
+      zs[t] = argmin 1/2 z'Hz + (F xs[t])'z over the box (oracle/qp.box_qp,
+        KKT-certified), to 1e-9 * max(1, |z_ref|) in fp64 and _tol32(H) * max(1,
+        |z_ref|) in fp32 (only the steps in z_steps, when given);
+      us[t] is zs[t][:nu], bitwise;
+      xs[t+1] = A xs[t] + B us[t], to 1e-12 * (1 + |x|) in fp64 and to
+        8 * eps32 * (|A||x| + |B||u|) in fp32 (nx + nu <= 6 FMAs per entry).
+    A, B, H, F are the instance's own (in fp32: of the fp32-rounded plant)."""
+    T, nu, n = us.shape[0], us.shape[2], zs.shape[2]
+    lbi, ubi = _bnd(lb, i, n), _bnd(ub, i, n)
+    tol = _tol32(H) if fp32 else 1e-9
+    for t in range(T):
+        x, u = xs[t, i], us[t, i]
+        if z_steps is None or t in z_steps:
+            f = F @ x
+            zr = oq.box_qp(H, f, lbi, ubi)[0]
+            assert oq.kkt_box(H, f, lbi, ubi, zr) < 1e-9 * max(1, np.abs(f).max()), (i, t)
+            err = np.abs(zs[t, i] - zr).max()
+            assert err < tol * max(1, np.abs(zr).max()), (i, t, err)
+        assert np.array_equal(u, zs[t, i, :nu]), (i, t)
+        xn = A @ x + B @ u
+        if fp32:
+            bound = 8 * EPS32 * (np.abs(A) @ np.abs(x) + np.abs(B) @ np.abs(u))
+            assert (np.abs(xs[t + 1, i] - xn) <= bound).all(), (i, t, xs[t + 1, i] - xn, bound)
+        else:
+            assert np.abs(xs[t + 1, i] - xn).max() < 1e-12 * (1 + np.abs(xn).max()), (i, t)
+
+
+def _episode(r):
+    torch.cuda.synchronize()
+    return {k: v.double().cpu().numpy() if k != "status" else v.cpu().numpy()
+            for k, v in r.items()}
+
+
+# (nx, nu, N): <2,1> BS 1 padded state | BS 2 | <2,2> n = 22 BS 6 | <4,2> padded
+# state and input BS 7 | BS 8 padded input | n = 32 | BS 1 in <4,2> | <2,2>
+# padded state
+LOOP_SHAPES = [(1, 1, 3), (2, 1, 8), (2, 2, 11), (3, 1, 25), (4, 1, 32), (3, 2, 16), (4, 2, 2),
+               (1, 2, 5)]
+LOOP_B, LOOP_T = 5, 6
+_loop_cache = {}
+
+
+def _loop_problem(nx, nu, N):
+    """Per-instance plants of spectral radius 1.02 and per-instance bounds
+    that differ along the horizon (x 4 on odd stages), with infinite and
+    fixed entries; the oracle's own closed loop from x0 (reference only: the
+    active sets along it), computed once per shape."""
+    key = (nx, nu, N)
+    if key in _loop_cache:
+        return _loop_cache[key]
+    # seed offset: one at which cond(H) <= 1e4 at every shape (asserted below; the
+    # fp32 tolerance needs it)
+    rng = np.random.default_rng(28 + 10000 * nx + 1000 * nu + N)
+    b, n = LOOP_B, N * nu
+    A = rng.normal(size=(b, nx, nx)) * (0.8 / np.sqrt(nx)) + 0.4 * np.eye(nx)
+    A *= (1.02 / np.abs(np.linalg.eigvals(A)).max(axis=-1))[:, None, None]
+    B = rng.normal(size=(b, nx, nu))
+    M = rng.normal(size=(nx, nx))
+    Q = M @ M.T / nx + 0.2 * np.eye(nx)
+    R = np.diag(rng.uniform(0.1, 1.0, nu))
+    x0 = 3 * rng.normal(size=(b, nx))
+    ub = rng.uniform(0.05, 0.3, (b, N, nu))
+    lb = -rng.uniform(0.05, 0.3, (b, N, nu))
+    ub[:, 1::2] *= 4
+    lb[:, 1::2] *= 4
+    lb, ub = lb.reshape(b, n), ub.reshape(b, n)
+    lb[rng.random((b, n)) < 0.10] = -np.inf
+    ub[rng.random((b, n)) < 0.10] = np.inf
+    fx = rng.random((b, n)) < 0.05
+    lb[fx] = ub[fx] = 0.02
+    p = dict(A=A, B=B, Q=Q, R=R, Qf=3 * Q, N=N, x0=x0, lb=lb, ub=ub)
+    p["cd"] = [oc.condense(A[i], B[i], Q, R, 3 * Q, N) for i in range(b)]
+    assert max(np.linalg.cond(d["H"]) for d in p["cd"]) <= 1e4
+    # the oracle's closed loop: active sets per step (0 free, 1 at lb, 2 at ub)
+    sets = np.zeros((b, LOOP_T, n), int)
+    for i in range(b):
+        x = x0[i]
+        for t in range(LOOP_T):
+            f = p["cd"][i]["F"] @ x
+            z = oq.box_qp(p["cd"][i]["H"], f, lb[i], ub[i])[0]
+            assert oq.kkt_box(p["cd"][i]["H"], f, lb[i], ub[i], z) < 1e-9 * max(1, np.abs(f).max())
+            sets[i, t] = np.where(z == lb[i], 1, np.where(z == ub[i], 2, 0))
+            x = A[i] @ x + B[i] @ z[:nu]
+    p["sets"] = sets
+    _loop_cache[key] = p
+    return p
+
+
+def test_loop_dispatch_reference_is_rich():
+    """On the reference alone: over the whole table at least half of the
+    (instance, step >= 1) pairs have an optimal active set that differs from
+    the previous one shifted one stage (the kernel's warm-start guess), and
+    every shape has a step with an active bound."""
+    differ = total = 0
+    for nx, nu, N in LOOP_SHAPES:
+        s = _loop_problem(nx, nu, N)["sets"]
+        assert (s != 0).any(), (nx, nu, N)
+        n = N * nu
+        src = np.minimum(np.arange(n) + nu, n - 1)
+        src = np.where(np.arange(n) + nu < n, src, np.arange(n))
+        for t in range(1, LOOP_T):
+            differ += int((s[:, t] != s[:, t - 1][:, src]).any(axis=1).sum())
+            total += s.shape[0]
+    print(f"active set differs from the shifted one in {differ} of {total} pairs")
+    assert total == len(LOOP_SHAPES) * LOOP_B * (LOOP_T - 1) and 2 * differ >= total
+
+
+@pytest.mark.parametrize("nx,nu,N", LOOP_SHAPES)
+def test_loop_dispatch_coverage(dev, nx, nu, N):
+    p = _loop_problem(nx, nu, N)
+    r = _episode(batched.mpc_box_loop(_t(p["A"], dev), _t(p["B"], dev), _t(p["Q"], dev),
+                                      _t(p["R"], dev), _t(p["Qf"], dev), N, _t(p["x0"], dev),
+                                      _t(p["lb"], dev), _t(p["ub"], dev), LOOP_T, plans=True))
+    assert ((r["status"] & 0xFF) == 0).all(), r["status"] & 0xFF
+    assert np.array_equal(r["xs"][0], p["x0"])
+    for i in range(LOOP_B):
+        _check_episode(p["A"][i], p["B"][i], p["cd"][i]["H"], p["cd"][i]["F"], p["lb"], p["ub"],
+                       r["xs"], r["us"], r["zs"], i)
+
+
+@pytest.mark.parametrize("nx,nu,N", [(2, 1, 20), (3, 2, 8)])
+@pytest.mark.parametrize("bounds", ["none", "lb_only"])
+def test_loop_unconstrained_and_one_sided(dev, nx, nu, N, bounds):
+    """No bounds: every plan is -H^-1 F x_t, the applied input the first move
+    of the finite-horizon LQR (oracle.session1.ricatti_recursion) and the
+    closed loop x_{t+1} = (A + B K_0) x_t; the status field counts the n sweeps
+    of the (all free) rows and no active-set iteration, at every step.  lb
+    only: the per-step oracle check."""
+    from oracle import session1 as s1
+
+    b, T, n = 6, 6, N * nu
+    if (nx, nu) == (2, 1):
+        A, B, Q, R, Qf = _fhc_plant()
+        x0 = np.random.default_rng(5).uniform(-10, 10, (b, 2))
+        As, Bs = np.broadcast_to(A, (b, 2, 2)), np.broadcast_to(B, (b, 2, 1))
+        At, Bt = A, B
+    else:
+        p = _loop_problem(nx, nu, N)
+        As, Bs, Q, R, Qf = p["A"], p["B"], p["Q"], p["R"], p["Qf"]
+        As, Bs = np.concatenate([As, As[:1] * 0.9]), np.concatenate([Bs, Bs[:1]])
+        x0 = 3 * np.random.default_rng(6).normal(size=(b, nx))
+        At, Bt = As, Bs
+    lb = None if bounds == "none" else -np.random.default_rng(7).uniform(0.05, 0.5, (b, n))
+    r = _episode(batched.mpc_box_loop(_t(At, dev), _t(Bt, dev), _t(Q, dev), _t(R, dev),
+                                      _t(Qf, dev), N, _t(x0, dev),
+                                      None if lb is None else _t(lb, dev), None, T, plans=True))
+    assert ((r["status"] & 0xFF) == 0).all()
+    nact = 0
+    for i in range(b):
+        d = oc.condense(As[i], Bs[i], Q, R, Qf, N)
+        _check_episode(As[i], Bs[i], d["H"], d["F"], lb, None, r["xs"], r["us"], r["zs"], i)
+        if bounds == "none":
+            K0 = s1.ricatti_recursion(As[i], Bs[i], Q, R, Qf, N)[1][0]
+            for t in range(T):
+                x = r["xs"][t, i]
+                z = -np.linalg.solve(d["H"], d["F"] @ x)
+                assert np.abs(r["zs"][t, i] - z).max() < 1e-9 * max(1, np.abs(z).max()), (i, t)
+                u = K0 @ x
+                assert np.abs(r["us"][t, i] - u).max() < 1e-9 * max(1, np.abs(u).max()), (i, t)
+                xn = (As[i] + Bs[i] @ K0) @ x
+                assert np.abs(r["xs"][t + 1, i] - xn).max() < TOL_X * (1 + np.abs(xn).max())
+        else:
+            nact += int((r["zs"][:, i] == lb[i]).sum())
+    if bounds == "none":
+        assert (((r["status"] >> 8) & 0xFFFF) == n).all(), (r["status"] >> 8) & 0xFFFF
+    else:
+        assert nact > 0
+
+
+def test_loop_statuses_nonfinite_state(dev):
+    """A NaN and an Inf in x0: NONFINITE (mpcqp.h: NaN/Inf in the data, what
+    mpcqp_mpc_box reports for the same input) at every step, NaN inputs, plans
+    and later states for that instance only; the healthy instances of the same
+    wavefront and of the next one equal the oracle."""
+    A, B, Q, R, Qf = _fhc_plant()
+    b, N, T = 6, 20, 4
+    x0 = np.random.default_rng(21).uniform(-10, 10, (b, 2))
+    x0[1, 1] = np.nan
+    x0[4, 0] = np.inf
+    r = _episode(batched.mpc_box_loop(_t(A, dev), _t(B, dev), _t(Q, dev), _t(R, dev), _t(Qf, dev),
+                                      N, _t(x0, dev), -1.0, 1.0, T, plans=True))
+    code = r["status"] & 0xFF
+    assert code.T.tolist() == [[0] * T, [4] * T, [0] * T, [0] * T, [4] * T, [0] * T], code
+    d = oc.condense(A, B, Q, R, Qf, N)
+    for i in range(b):
+        if i in (1, 4):
+            assert np.array_equal(r["xs"][0, i], x0[i], equal_nan=True)
+            assert np.isnan(r["us"][:, i]).all() and np.isnan(r["zs"][:, i]).all(), i
+            assert np.isnan(r["xs"][1:, i]).all(), i
+        else:
+            _check_episode(A, B, d["H"], d["F"], -1.0, 1.0, r["xs"], r["us"], r["zs"], i)
+            hx, hu = _host_loop(A, B, Q, R, Qf, N, x0[i], -np.ones(N), np.ones(N), T)
+            assert np.abs(r["xs"][:, i] - hx).max() < TOL_X * (1 + np.abs(hx).max()), i
+            assert np.abs(r["us"][:, i] - hu).max() < TOL_X, i
+
+
+def test_loop_statuses_condensed(dev):
+    """Through condensed=: a NaN in H or in F gives NONFINITE and an indefinite
+    H (one diagonal entry negated) NOT_CONVEX, at every step; their neighbours
+    are unaffected."""
+    A, B, Q, R, Qf = _fhc_plant()
+    b, N, T = 6, 20, 4
+    x0 = np.random.default_rng(22).uniform(-10, 10, (b, 2))
+    Ab, Bb = np.broadcast_to(A, (b, 2, 2)), np.broadcast_to(B, (b, 2, 1))
+    cd = batched.condense(_t(Ab, dev), _t(Bb, dev), _t(Q, dev), _t(R, dev), _t(Qf, dev), N,
+                          outputs=("H", "F"))
+    H = cd["H"].clone()
+    H[2, 7 * 8 // 2 + 7] *= -1.0          # packed (7, 7)
+    H[4, 100] = float("nan")
+    F = cd["F"].clone()
+    F[5, 13, 1] = float("nan")
+    d = oc.condense(A, B, Q, R, Qf, N)
+    Hbad = d["H"].copy()
+    Hbad[7, 7] *= -1.0
+    assert np.linalg.eigvalsh(Hbad).min() < 0
+    r = _episode(batched.mpc_box_loop(_t(Ab, dev), _t(Bb, dev), _t(Q, dev), _t(R, dev),
+                                      _t(Qf, dev), N, _t(x0, dev), -1.0, 1.0, T, plans=True,
+                                      condensed={"H": H, "F": F}))
+    code = r["status"] & 0xFF
+    assert code.T.tolist() == [[0] * T, [0] * T, [2] * T, [0] * T, [4] * T, [4] * T], code
+    for i in range(b):
+        if i in (2, 4, 5):
+            assert np.isnan(r["us"][:, i]).all() and np.isnan(r["zs"][:, i]).all(), i
+        else:
+            _check_episode(A, B, d["H"], d["F"], -1.0, 1.0, r["xs"], r["us"], r["zs"], i)
+
+
+def test_loop_max_iter(dev):
+    """max_iter = 2 on the config-2 plant from x0 in +-10: some steps end in
+    MAXITER, every plan is finite and inside the box, every optimal step is the
+    oracle's, and the episode runs all T steps."""
+    A, B, Q, R, Qf = _fhc_plant()
+    b, N, T = 8, 20, 8
+    x0 = np.random.default_rng(23).uniform(-10, 10, (b, 2))
+    r = _episode(batched.mpc_box_loop(_t(A, dev), _t(B, dev), _t(Q, dev), _t(R, dev), _t(Qf, dev),
+                                      N, _t(x0, dev), -1.0, 1.0, T, plans=True, max_iter=2))
+    code = r["status"] & 0xFF
+    assert np.isin(code, (0, 1)).all(), code
+    assert (code == 1).any(), code
+    assert np.isfinite(r["zs"]).all() and np.abs(r["zs"]).max() <= 1.0
+    assert np.isfinite(r["xs"]).all() and r["xs"].shape[0] == T + 1
+    d = oc.condense(A, B, Q, R, Qf, N)
+    for i in range(b):
+        _check_episode(A, B, d["H"], d["F"], -1.0, 1.0, r["xs"], r["us"], r["zs"], i,
+                       z_steps=set(np.nonzero(code[:, i] == 0)[0].tolist()))
+
+
+@pytest.mark.parametrize("nx,nu,N", [(2, 1, 8), (3, 1, 25), (3, 2, 16)])
+def test_loop_fp32(dev, nx, nu, N):
+    """fp32 episodes (T = 5) at the fp32 tolerance of the fused step, against
+    the fp64 oracle on the fp32-rounded plant at the device's states."""
+    p = _loop_problem(nx, nu, N)
+    T, f32 = 5, torch.float32
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=f32, device=dev)  # noqa: E731
+    r = _episode(batched.mpc_box_loop(t(p["A"]), t(p["B"]), t(p["Q"]), t(p["R"]), t(p["Qf"]), N,
+                                      t(p["x0"]), t(p["lb"]), t(p["ub"]), T, plans=True))
+    assert ((r["status"] & 0xFF) == 0).all(), r["status"] & 0xFF
+    A32 = p["A"].astype(np.float32).astype(np.float64)
+    B32 = p["B"].astype(np.float32).astype(np.float64)
+    for i in range(LOOP_B):
+        d = oc.condense(A32[i], B32[i], p["Q"], p["R"], p["Qf"], N)
+        _check_episode(A32[i], B32[i], d["H"], d["F"], p["lb"], p["ub"], r["xs"], r["us"],
+                       r["zs"], i, fp32=True)
+
+
+@pytest.mark.parametrize("nx,nu,N", [(2, 1, 20), (4, 2, 8)])
+def test_loop_shared_vs_broadcast_plant(dev, nx, nu, N):
+    """A, B shared (stride 0, H and F condensed once) against the same plant
+    broadcast per instance: bitwise equal states, inputs and status words."""
+    b, T = 7, 6
+    rng = np.random.default_rng(24 + nx)
+    if nx == 2:
+        A, B, Q, R, Qf = _fhc_plant()
+        x0, lo, hi = rng.uniform(-10, 10, (b, 2)), -1.0, 1.0
+    else:
+        p = _loop_problem(4, 2, 2)
+        A, B, Q, R, Qf = p["A"][0], p["B"][0], p["Q"], p["R"], p["Qf"]
+        x0, lo, hi = 3 * rng.normal(size=(b, nx)), -0.2, 0.3
+    rs = _episode(batched.mpc_box_loop(_t(A, dev), _t(B, dev), _t(Q, dev), _t(R, dev),
+                                       _t(Qf, dev), N, _t(x0, dev), lo, hi, T))
+    rb = _episode(batched.mpc_box_loop(_t(np.broadcast_to(A, (b, nx, nx)), dev),
+                                       _t(np.broadcast_to(B, (b, nx, nu)), dev), _t(Q, dev),
+                                       _t(R, dev), _t(Qf, dev), N, _t(x0, dev), lo, hi, T))
+    assert ((rs["status"] & 0xFF) == 0).all()
+    assert ((rs["us"] == lo) | (rs["us"] == hi)).any()     # the bounds do act
+    for k in ("xs", "us", "status"):
+        assert np.array_equal(rs[k], rb[k]), k
+
+
+def test_loop_status_precedence(dev):
+    """NONFINITE goes before INFEASIBLE where both hold at the first step (as
+    in the other kernels); an empty box alone stays INFEASIBLE at every step,
+    although its states are NaN after the first one."""
+    A, B, Q, R, Qf = _fhc_plant()
+    b, N, T = 5, 10, 3
+    x0 = np.random.default_rng(25).uniform(-10, 10, (b, 2))
+    lb, ub = -np.ones((b, N)), np.ones((b, N))
+    lb[1, 4] = lb[3, 0] = 2.0
+    x0[3, 0] = np.nan
+    r = _episode(batched.mpc_box_loop(_t(A, dev), _t(B, dev), _t(Q, dev), _t(R, dev), _t(Qf, dev),
+                                      N, _t(x0, dev), _t(lb, dev), _t(ub, dev), T, plans=True))
+    code = r["status"] & 0xFF
+    assert code.T.tolist() == [[0] * T, [3] * T, [0] * T, [4] * T, [0] * T], code
+    assert np.isnan(r["xs"][1:, [1, 3]]).all() and np.isnan(r["zs"][:, [1, 3]]).all()
+    d = oc.condense(A, B, Q, R, Qf, N)
+    for i in (0, 2, 4):
+        _check_episode(A, B, d["H"], d["F"], lb, ub, r["xs"], r["us"], r["zs"], i)
