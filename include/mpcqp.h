@@ -91,6 +91,9 @@ extern "C" {
    elements per instance instead of N*nx*N*nu (the upper block triangle is
    structurally zero; SURVEY 8(d) counts only this part) */
 #define MPCQP_GAM_PACKED 8
+/* mpcqp_mpc_poly_loop: every step starts cold (W = M, empty active set)
+   instead of from the previous step's active set */
+#define MPCQP_LOOP_COLD 16
 
 /* status bit 24: the solution was polished to the exact active-set vertex */
 #define MPCQP_STATUS_POLISHED (1 << 24)
@@ -576,6 +579,50 @@ int mpcqp_mpc_box_loop(int dtype, int batch, int nx, int nu, int N, int steps,
                        const void* x0, int64_t strideX0, const void* lb, int64_t strideLb,
                        const void* ub, int64_t strideUb, void* xs, void* us, void* zs,
                        int32_t* status, int max_iter, double tol, void* stream);
+
+/*
+ * The receding-horizon loop of a linear MPC with row (state) constraints and
+ * an input box, T steps in one launch: the MPC of sessions 2 and 3
+ * (session_2/problem.py:4-33: double integrator, input box and the state box
+ * p_max, v_min, v_max; per-step record session_2/log.py:8-12, whose
+ * solver_success is the status word) on a linear plant
+ * (LinearSystem.py:20-26; the state box as rows with bounds shifted by the
+ * free response, main.py:58-61; simulate(...) main.py:270-271):
+ *   for t = 0..steps-1:
+ *     z_t = argmin 1/2 z'Hz + (F x_t)'z
+ *           s.t.  hl - E x_t <= G z <= hu - E x_t,  lbz <= z <= ubz
+ *     u_t = z_t[0..nu-1],  x_{t+1} = A x_t + B u_t (+ w_t)
+ * workspace: the factors of mpcqp_poly_setup(H, G, F) with the same n, m,
+ * nbox, nx (read-only).  With G = Gam, E = Phi, hl/hu = tile(x_min/x_max, N)
+ * this is the state box on x_1..x_N; E = NULL leaves the rows fixed (BASELINE
+ * config 4).  A (nx x nx), Bm (nx x nu): the simulated plant, shared; it may
+ * differ from the model behind H and F.  hl/hu (m; strideh 0 = shared; NULL =
+ * -inf/+inf), lbz/ubz (n, shared, used when nbox = 1), w (optional, steps x
+ * batch x nx: plant disturbance).  flags: MPCQP_LOOP_COLD.
+ * Outputs: xs ((steps+1) x batch x nx, xs[0] = x0), us (steps x batch x nu),
+ * zs (optional, steps x batch x n: the plans), ys (optional, steps x batch x
+ * m_total: row multipliers, signs as in mpcqp_poly_solve), status (steps x
+ * batch; bits 8..23 = active-set iterations of the step, warm-start repairs
+ * and rebuild sweeps included); us and status may be NULL when steps = 0.
+ * Each step is warm-started from the previous step's final active set.
+ * Limits: m_total = m + (nbox ? n : 0) in [1, 64], nx <= 16, nu <= min(16, n).
+ * max_iter = 0: 4*m_total + 40.
+ * Status codes of a step (bits 0..7): OPTIMAL; MAXITER (the iterate is used,
+ * the loop goes on); NOT_CONVEX (the setup's flag, or a non-positive pivot);
+ * INFEASIBLE (the step's QP is empty, hl > hu on a row, or an infinite bound
+ * on the wrong side); NONFINITE (NaN/Inf in x_t, the bounds or w_t);
+ * NONFINITE goes before INFEASIBLE before NOT_CONVEX.  A step that ends in
+ * one of the last three writes NaN to us, zs, ys and hence to x_{t+1}; every
+ * later step of that instance repeats the first failure's code; the other
+ * instances are not affected.
+ */
+int mpcqp_mpc_poly_loop(int dtype, int batch, int n, int m, int nbox, int nx, int nu, int steps,
+                        int flags, const void* workspace, const void* E,
+                        const void* A, const void* Bm, const void* x0, int64_t strideX0,
+                        const void* hl, const void* hu, int64_t strideh,
+                        const void* lbz, const void* ubz, const void* w,
+                        void* xs, void* us, void* zs, void* ys, int32_t* status,
+                        int max_iter, double tol, void* stream);
 
 /*
  * Batched finite-horizon Riccati recursion, FHC.py:51-61:

@@ -24,7 +24,7 @@ import torch
 from . import _native as nat
 
 __all__ = [
-    "condense", "solve_box", "mpc_box", "mpc_box_loop", "mpc_qp", "mpc_ipm", "solve_poly", "solve_qp", "sweep", "riccati", "gemv",
+    "condense", "solve_box", "mpc_box", "mpc_box_loop", "mpc_poly_loop", "mpc_qp", "mpc_ipm", "solve_poly", "solve_qp", "sweep", "riccati", "gemv",
     "rollout", "bicycle_rti", "bicycle_linearise", "bicycle_hessian", "bicycle_sqp_step",
     "pack_lower", "unpack_lower", "status_code", "status_iters", "workspace_bytes",
 ]
@@ -584,6 +584,117 @@ class PolyQP:
                                      _ptr(status), int(max_iter), float(tol), _stream())
         nat.check(rc, "mpcqp_poly_solve")
         return z, y, status
+
+    def loop(self, A, B, x0, steps: int, hl=None, hu=None, E=None, w=None, *,
+             plans: bool = False, multipliers: bool = False, cold: bool = False,
+             max_iter: int = 0, tol: float = 0.0, out: dict | None = None) -> dict:
+        """The receding-horizon loop on this object's factors, ``steps`` steps
+        in one launch (include/mpcqp.h ``mpcqp_mpc_poly_loop``): per step
+        z_t = argmin 1/2 z'Hz + (F x_t)'z over hl - E x_t <= G z <= hu - E x_t,
+        lbz <= z <= ubz; u_t = z_t[:nu]; x_{t+1} = A x_t + B u_t (+ w_t).
+
+        A (nx, nx), B (nx, nu): the simulated plant (shared); x0 (b, nx); hl, hu
+        (m,) | (b, m); E (m, nx) or None; w (steps, b, nx) or None.  Each step
+        starts from the previous step's active set unless ``cold``.  Returns
+        xs (steps+1, b, nx), us (steps, b, nu), status (steps, b), with
+        ``plans`` zs (steps, b, n), with ``multipliers`` ys (steps, b, m_total)."""
+        dt, dev, n, m, nx = self.dtype, self.device, self.n, self.m, self.nx
+        if nx == 0:
+            raise ValueError("PolyQP.loop needs the x0 -> gradient map F at construction")
+        A, B, x0 = _dev(A, dt, dev), _dev(B, dt, dev), _dev(x0, dt, dev)
+        if tuple(A.shape) != (nx, nx):
+            raise ValueError(f"A must be ({nx}, {nx}), got {tuple(A.shape)}")
+        if B.ndim != 2 or B.shape[0] != nx:
+            raise ValueError(f"B must be ({nx}, nu), got {tuple(B.shape)}")
+        nu = int(B.shape[1])
+        if not 1 <= nu <= min(16, n):
+            raise ValueError(f"nu={nu} outside [1, min(16, n={n})]")
+        if x0.ndim != 2 or x0.shape[1] != nx:
+            raise ValueError(f"x0 must be (batch, {nx}), got {tuple(x0.shape)}")
+        batch, T = int(x0.shape[0]), int(steps)
+        if T < 0:
+            raise ValueError(f"steps={T} < 0")
+        hl, hu = _dev(hl, dt, dev), _dev(hu, dt, dev)
+        sh = 0
+        for name, h in (("hl", hl), ("hu", hu)):
+            if h is None:
+                continue
+            if h.shape[-1] != m or h.ndim not in (1, 2) or (h.ndim == 2 and h.shape[0] != batch):
+                raise ValueError(f"{name} must be ({m},) or ({batch}, {m}), got {tuple(h.shape)}")
+            sh = max(sh, m if h.ndim == 2 else 0)
+        if hl is not None and hu is not None and hl.ndim != hu.ndim:
+            raise ValueError("hl and hu must both be shared or both per instance")
+        E = _dev(E, dt, dev)
+        if E is not None and tuple(E.shape) != (m, nx):
+            raise ValueError(f"E must be ({m}, {nx}), got {tuple(E.shape)}")
+        w = _dev(w, dt, dev)
+        if w is not None and tuple(w.shape) != (T, batch, nx):
+            raise ValueError(f"w must be ({T}, {batch}, {nx}), got {tuple(w.shape)}")
+        o = dict(out or {})
+        shapes = dict(xs=((T + 1, batch, nx), dt), us=((T, batch, nu), dt),
+                      status=((T, batch), torch.int32))
+        if plans:
+            shapes["zs"] = ((T, batch, n), dt)
+        if multipliers:
+            shapes["ys"] = ((T, batch, self.mt), dt)
+        for k, (shp, kd) in shapes.items():
+            if k not in o:
+                o[k] = torch.empty(shp, dtype=kd, device=dev)
+            elif tuple(o[k].shape) != shp or o[k].dtype != kd or not o[k].is_contiguous():
+                raise ValueError(f"out[{k!r}] must be a contiguous {kd} tensor of shape {shp}")
+        rc = _lib().mpcqp_mpc_poly_loop(
+            _code(dt), batch, n, m, self.nbox, nx, nu, T, nat.LOOP_COLD if cold else 0,
+            _ptr(self.ws), _ptr(E), _ptr(A), _ptr(B), _ptr(x0), nx, _ptr(hl), _ptr(hu), sh,
+            _ptr(self.lbz), _ptr(self.ubz), _ptr(w), _ptr(o["xs"]), _ptr(o["us"]),
+            _ptr(o.get("zs")), _ptr(o.get("ys")), _ptr(o["status"]), int(max_iter), float(tol),
+            _stream())
+        nat.check(rc, "mpcqp_mpc_poly_loop")
+        return o
+
+
+def mpc_poly_loop(A, B, Q, R, Qf, N: int, x0, xlo=None, xhi=None, lb=None, ub=None,
+                  steps: int = 1, *, plant=None, w=None, plans: bool = False,
+                  multipliers: bool = False, cold: bool = False, max_iter: int = 0,
+                  tol: float = 0.0) -> dict:
+    """The receding-horizon loop of the linear MPC with a state box on
+    x_1..x_N and an input box (sessions 2 and 3, session_2/problem.py:4-33), on
+    the device in one launch.  The shared model (A, B) is condensed once (H, F,
+    Gam, Phi); the state box becomes the rows xlo - Phi x_t <= Gam z <= xhi -
+    Phi x_t of a ``PolyQP`` (G = Gam, E = Phi), lb/ub (scalar, (nu,) or
+    (N*nu,)) its input box, and ``PolyQP.loop`` runs the episode.
+    ``plant=(A_p, B_p)`` simulates another plant than the controller's model.
+    x0 (b, nx); xlo/xhi (nx,) or None.  Returns the dict of ``PolyQP.loop``
+    plus ``condensed`` (H, F, Gam, Phi of the model, unbatched)."""
+    dt = A.dtype if isinstance(A, torch.Tensor) else torch.float64
+    dev = A.device if isinstance(A, torch.Tensor) else torch.device("cuda")
+    A, B = _dev(A, dt, dev), _dev(B, dt, dev)
+    if A.ndim != 2 or B.ndim != 2:
+        raise ValueError("mpc_poly_loop: the model (A, B) is shared by the batch")
+    nx, nu = int(B.shape[0]), int(B.shape[1])
+    n = N * nu
+    cd = condense(A, B, Q, R, Qf, N, outputs=("H", "F", "Gam", "Phi"))
+    cd = {k: v[0] for k, v in cd.items()}
+
+    def stage_bound(v, width, name):
+        if v is None:
+            return None
+        t = torch.as_tensor(v, dtype=dt, device=dev)
+        if t.ndim == 0 or tuple(t.shape) == (width,):
+            return t.expand(width).repeat(N)
+        if tuple(t.shape) == (N * width,):
+            return t
+        raise ValueError(f"{name}: expected a scalar, ({width},) or ({N * width},), "
+                         f"got {tuple(t.shape)}")
+
+    hl, hu = stage_bound(xlo, nx, "xlo"), stage_bound(xhi, nx, "xhi")
+    rows = hl is not None or hu is not None
+    qp = PolyQP(cd["H"], cd["Gam"] if rows else None, cd["F"], stage_bound(lb, nu, "lb"),
+                stage_bound(ub, nu, "ub"))
+    Ap, Bp = (A, B) if plant is None else plant
+    o = qp.loop(Ap, Bp, x0, steps, hl, hu, cd["Phi"] if rows else None, w, plans=plans,
+                multipliers=multipliers, cold=cold, max_iter=max_iter, tol=tol)
+    o["condensed"] = cd
+    return o
 
 
 # ------------------------------------------ general QP, per-instance rows

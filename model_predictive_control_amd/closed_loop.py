@@ -201,3 +201,47 @@ def lti_box_mpc_loop(A, B, Q, R, Qf, N: int, X0, lb, ub, steps: int) -> dict:
     return {"xs": r["xs"], "us": r["us"], "success": batched.status_code(r["status"]) == 0,
             "iters": batched.status_iters(r["status"]),
             "input_prediction": r["zs"].reshape(steps, X0.shape[0], N, nu)}
+
+
+def lti_mpc_loop(problem, X0, steps: int, *, N: int | None = None, Qf=None, plant=None, w=None,
+                 cold: bool = False, max_iter: int = 0, tol: float = 0.0) -> dict:
+    """The receding-horizon loop of the state- and input-constrained linear MPC
+    of sessions 2 and 3 (session_2/problem.py:4-33) on a linear plant, all
+    ``steps`` in one launch (``batched.mpc_poly_loop``).  ``problem`` is a
+    ``problems.Problem`` (A, B, Q, R, the state box x_min/x_max on x_1..x_N,
+    the input box u_min/u_max, horizon N; terminal weight ``Qf``, default Q) or
+    a dict with the keys A, B, Q, R, N and optionally Qf, xlo, xhi, lb, ub.
+    ``plant=(A_p, B_p)`` simulates another plant than the model; ``w`` (T, b,
+    nx) is a plant disturbance.  X0 (b, nx) -> the ControllerLog fields
+    (session_2/log.py:8-12) batched: success (T, b) (solver_success),
+    input_prediction (T, b, N, nu), state_prediction (T, b, N+1, nx) = [x_t;
+    Phi x_t + Gam z_t]; and xs (T+1, b, nx), us (T, b, nu), status, iters."""
+    dev = torch.device("cuda")
+    t = lambda a: None if a is None else torch.as_tensor(a, dtype=torch.float64, device=dev)  # noqa: E731
+    if isinstance(problem, dict):
+        p = problem
+        A, B, Q, R = t(p["A"]), t(p["B"]), t(p["Q"]), t(p["R"])
+        N = int(p["N"] if N is None else N)
+        Qf = p.get("Qf") if Qf is None else Qf
+        xlo, xhi, lb, ub = p.get("xlo"), p.get("xhi"), p.get("lb"), p.get("ub")
+    else:
+        A, B, Q, R = t(problem.A), t(problem.B), t(problem.Q), t(problem.R)
+        N = int(problem.N if N is None else N)
+        xlo, xhi = problem.x_min, problem.x_max
+        lb, ub = float(problem.u_min), float(problem.u_max)
+    Qf = Q if Qf is None else t(Qf)
+    nx, nu = int(B.shape[0]), int(B.shape[1])
+    X0 = t(X0).reshape(-1, nx)
+    T, b = int(steps), int(X0.shape[0])
+    if plant is not None:
+        plant = (t(plant[0]), t(plant[1]))
+    r = batched.mpc_poly_loop(A, B, Q, R, Qf, N, X0, t(xlo), t(xhi), lb, ub, T, plant=plant,
+                              w=t(w), plans=True, cold=cold, max_iter=max_iter, tol=tol)
+    cd = r["condensed"]
+    xs, zs = r["xs"], r["zs"]
+    pred = xs[:T] @ cd["Phi"].T + zs @ cd["Gam"].T                 # (T, b, N*nx)
+    state_prediction = torch.cat([xs[:T].unsqueeze(2), pred.reshape(T, b, N, nx)], dim=2)
+    return {"xs": xs, "us": r["us"], "status": r["status"],
+            "success": batched.status_code(r["status"]) == 0,
+            "iters": batched.status_iters(r["status"]),
+            "input_prediction": zs.reshape(T, b, N, nu), "state_prediction": state_prediction}

@@ -1,0 +1,485 @@
+// loop_poly.hip -- mpcqp_mpc_poly_loop: the receding-horizon loop of a linear
+// MPC with row (state) constraints and an input box, T steps in ONE launch, one
+// instance per wavefront.
+//
+// Reference: the MPC of sessions 2 and 3 (session_2/problem.py:4-33: a double
+// integrator with p_max, v_min, v_max and an input box; the per-step
+// ControllerLog of session_2/log.py:8-12, whose solver_success is the status
+// word here) run in closed loop on a linear plant (LinearSystem.py:20-26;
+// simulate(...) main.py:270-271), with the state box in condensed form as
+// rows of Gam with bounds shifted by the free response (main.py:58-61).  Per
+// step t and instance b:
+//   z_t = argmin 1/2 z'Hz + (F x_t)'z   s.t.  hl - E x_t <= G z <= hu - E x_t,
+//                                              lbz <= z <= ubz
+//   u_t = z_t[0..nu-1],   x_{t+1} = A x_t + B u_t (+ w_t)
+//
+// The QP is solved through its dual as in solve_poly.hip (dual range active
+// set on W = SWEEP_A(M), register-resident on the Sym2D grid), on the shared
+// factors of mpcqp_poly_setup.  Everything a step needs stays on chip for the
+// whole episode: packed M, L, E, the plant and the first nu columns of Ut and
+// Kt in LDS, W and the row states in registers.  Per step the HBM traffic is
+// x, u, the status word and the optional w / zs / ys.
+//
+// Warm start: W and the row states st carry over, unshifted.  At the top of a
+// step y is recomputed for the new s0 and bounds; while an active row's
+// multiplier has the wrong sign for its side, the most wrong row is dropped
+// (a reverse sweep) -- at most |A| drops, after which (z(A), y) is a
+// dual-feasible pair and the ordinary iteration continues from it.
+//
+// Drift: W is reloaded from the LDS copy of M whenever a step ends with an
+// empty active set, and rebuilt (reload, then the active rows swept back in)
+// every kPolyLoopRebuild steps.
+//
+// The step is one loop with ONE sweep site (rebuild adds, repair drops and the
+// iteration's adds and drops all pass through it), so that W lives in a single
+// register set, as in dual_range_kernel.  Every trip counts against max_iter,
+// except the rebuild sweeps, which a bit mask of at most mt rows bounds; every
+// exit test is written so that a NaN operand ends the loop.
+#include "poly_ws.hpp"
+#include "sym2d.hpp"
+
+// Steps between two rebuilds of W from M ("Poly loop").
+#ifndef MPCQP_POLY_LOOP_REBUILD
+#define MPCQP_POLY_LOOP_REBUILD 64
+#endif
+
+namespace mpcqp {
+
+constexpr int kPolyLoopRebuild = MPCQP_POLY_LOOP_REBUILD;
+
+template <typename T>
+struct PolyLoopArgs {
+  int batch, n, m, mt, nx, nu, steps, cold;
+  const T* M;                  // packed lower mt x mt
+  const T* Ut;                 // mt x n
+  const T* Kt;                 // nx x n
+  const T* L;                  // mt x nx
+  const int32_t* flag;         // set by the shared inverse when H is not PD
+  const T* E;                  // m x nx or null
+  const T* A; const T* B;      // plant
+  const T* x0; int64_t sX0;
+  const T* hl; const T* hu; int64_t sh;
+  const T* lbz; const T* ubz;
+  const T* w;                  // steps x batch x nx or null
+  T* xs; T* us; T* zs; T* ys;
+  int32_t* status;
+  int max_iter;
+  T tol;
+};
+
+// LDS elements of the loop kernel: Sym2D scratch, the mat-vec partials, packed
+// M, L' and E' (nx x NMAX each, transposed: lane = row reads conflict-free),
+// A, B, the first nu columns of Ut (NMAX x nu) and Kt (nx x nu), x_t, u_t.
+__host__ __device__ inline int poly_loop_lds(int BS, int mt, int nx, int nu) {
+  const int NMAX = 8 * BS;
+  return NMAX * BS + NMAX + 8 * NMAX + mt * (mt + 1) / 2 + 2 * nx * NMAX + nx * nx + nx * nu +
+         NMAX * nu + nx * nu + 32;
+}
+
+// z_j = Kt[:, j]' x - sum over the rows with y != 0 of Ut[r][j] y_r: the
+// epilogue of dual_range_kernel.  One function for the plan (global Ut, Kt)
+// and for the applied input (their LDS copies), so that u_t equals z_t[0..nu)
+// bit for bit.
+template <typename T>
+__device__ __forceinline__ T poly_epilogue(const T* Kt, const T* Ut, int64_t ld, int j, int nx,
+                                           const T* x, T yi, uint64_t yact) {
+  T acc = T(0);
+  for (int k = 0; k < nx; ++k) acc = fma(Kt[(int64_t)k * ld + j], x[k], acc);
+  for (uint64_t mk = yact; mk; mk &= mk - 1) {
+    const int r = uniform(__builtin_ctzll(mk));
+    acc = fma(-Ut[(int64_t)r * ld + j], readlane(yi, r), acc);
+  }
+  return acc;
+}
+
+// st: 0 inactive, 1 at lower, 2 at upper, 3 padding row; row-indexed vectors
+// one row per lane, as in dual_range_kernel.
+template <typename T, int BS>
+__global__ __launch_bounds__(64) void poly_loop_kernel(PolyLoopArgs<T> a) {
+  using S2 = Sym2D<T, BS>;
+  constexpr int NMAX = S2::NMAX;
+  static_assert(NMAX <= kWave, "one row per lane");
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int b = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int mt = a.mt, m = a.m, nz = a.n, nx = a.nx, nu = a.nu;
+  const int P = mt * (mt + 1) / 2;
+  T* buf = reinterpret_cast<T*>(smem_raw);
+  T* part = buf + S2::BUF;
+  T* Ps = part + 8 * NMAX;
+  T* Lt = Ps + P;
+  T* Et = Lt + nx * NMAX;
+  T* As = Et + nx * NMAX;
+  T* Bs = As + nx * nx;
+  T* Un = Bs + nx * nu;
+  T* Kn = Un + NMAX * nu;
+  T* xl = Kn + nx * nu;
+  T* ul = xl + 16;
+
+  // ------------------------------------------------------------- stage in
+  stage_packed<T, NMAX*(NMAX + 1) / 2>(a.M, Ps, P, lane);
+  for (int e = lane; e < nx * NMAX; e += kWave) {
+    const int k = e / NMAX, r = e - k * NMAX;
+    Lt[e] = r < mt ? a.L[r * nx + k] : T(0);
+    Et[e] = (a.E && r < m) ? a.E[r * nx + k] : T(0);
+  }
+  for (int e = lane; e < nx * nx; e += kWave) As[e] = a.A[e];
+  for (int e = lane; e < nx * nu; e += kWave) {
+    const int k = e / nu, j = e - k * nu;
+    Bs[e] = a.B[e];
+    Kn[e] = a.Kt[(int64_t)k * nz + j];
+  }
+  for (int e = lane; e < NMAX * nu; e += kWave) {
+    const int r = e / nu, j = e - r * nu;
+    Un[e] = r < mt ? a.Ut[(int64_t)r * nz + j] : T(0);
+  }
+  if (lane < 16) {
+    xl[lane] = lane < nx ? a.x0[(int64_t)b * a.sX0 + lane] : T(0);
+    ul[lane] = T(0);
+  }
+  __syncthreads();
+
+  // row `lane`: bounds (rows < m per instance or shared, the box rows shared), M_ii
+  const bool row = lane < mt;
+  T li = -Lim<T>::inf(), ui = Lim<T>::inf(), md = T(1);
+  if (row) {
+    if (lane < m) {
+      if (a.hl) li = a.hl[(int64_t)b * a.sh + lane];
+      if (a.hu) ui = a.hu[(int64_t)b * a.sh + lane];
+    } else {
+      if (a.lbz) li = a.lbz[lane - m];
+      if (a.ubz) ui = a.ubz[lane - m];
+    }
+    md = Ps[lane * (lane + 1) / 2 + lane];
+  }
+  bool nf0 = row && (li != li || ui != ui);
+  for (int e = lane; e < P; e += kWave) nf0 |= !finite(Ps[e]);
+  const bool badbox =
+      row && (!(li <= ui) || li == Lim<T>::inf() || ui == -Lim<T>::inf());
+  // NONFINITE, then INFEASIBLE, then NOT_CONVEX
+  const int code0 = __any(nf0) ? MPCQP_STATUS_NONFINITE
+                    : __any(badbox) ? MPCQP_STATUS_INFEASIBLE
+                    : *a.flag ? MPCQP_STATUS_NOT_CONVEX
+                              : MPCQP_STATUS_OPTIMAL;
+
+  S2 W;
+  W.init(lane);
+  int st = row ? 0 : 3;
+  T yi = T(0), si = T(0);
+  const T tol = a.tol;
+  const T dep_tol = sizeof(T) == 8 ? T(1e-10) : T(1e-5);
+  const int max_iter = a.max_iter;
+  int failed = MPCQP_STATUS_OPTIMAL;  // code of the instance's first failed step
+  bool reload = true;                 // W <- M at the top of the step ...
+  uint64_t rmask = 0;                 // ... then these rows swept back in
+  bool fresh = false;                 // W is exactly M
+  int since = 0;                      // steps since W was last loaded from M
+
+  for (int t = 0; t < a.steps; ++t) {
+    const int64_t tb = (int64_t)t * a.batch + b;
+    // record x_t; the step's disturbance; s0 = L x_t, the rows' shift E x_t
+    T wv = T(0);
+    bool nf = false;
+    if (lane < nx) {
+      const T xv = xl[lane];
+      a.xs[tb * nx + lane] = xv;
+      if (a.w) wv = a.w[tb * nx + lane];
+      nf = !finite(xv) || !finite(wv);
+    }
+    T s0 = T(0), ex = T(0);
+    if (row) {
+      for (int k = 0; k < nx; ++k) {
+        const T xk = xl[k];
+        s0 = fma(Lt[k * NMAX + lane], xk, s0);
+        ex = fma(Et[k * NMAX + lane], xk, ex);
+      }
+      nf |= !finite(s0) || !finite(ex);
+    }
+    const T lt = li - ex, ut = ui - ex;
+    // relative-violation scales 1/(1+|bound|), NaN for an infinite bound (a NaN
+    // violation never wins the arg-max)
+    const T sl = finite(lt) ? T(1) / (T(1) + fabs(lt)) : T(__builtin_nan(""));
+    const T su = finite(ut) ? T(1) / (T(1) + fabs(ut)) : T(__builtin_nan(""));
+
+    int code = __any(nf) ? MPCQP_STATUS_NONFINITE : code0;
+    if (failed != MPCQP_STATUS_OPTIMAL) code = failed;
+    int iters = 0;
+    yi = T(0);
+
+    if (code == MPCQP_STATUS_OPTIMAL) {
+      if (reload) {
+        bool unused = false;
+        W.load_packed(Ps, mt, unused);
+        fresh = rmask == 0;
+        since = 0;
+      }
+      // w = (s0 - b on active rows, 0 elsewhere);  v = W w;
+      // active: y = -v, s = bound;  inactive: s = s0 - v
+      auto refresh = [&]() {
+        const bool act = st == 1 || st == 2;
+        const T bnd = (st == 1) ? lt : ut;
+        const T v = matvec_lane_lds<T, BS>(W, act ? s0 - bnd : T(0), buf, part);
+        yi = act ? -v : T(0);
+        si = act ? bnd : s0 - v;
+      };
+      // phase 0: sweep the rows of rmask back into the reloaded W;
+      // phase 1: drop the active rows whose multiplier has the wrong sign;
+      // phase 2: the dual range active set of dual_range_kernel
+      int phase = rmask ? 0 : 1;
+      if (phase == 1) refresh();
+      bool havep = false;
+      int p = 0, side = 0;
+      T sp = T(0), tgt = T(0), ysgn = T(0), mpp = T(1);
+      code = MPCQP_STATUS_MAXITER;
+      while (true) {
+        int idx = 0;
+        T sig = T(1), d = T(1);
+        T c[BS], cc[BS];
+        bool add = false, op = false, stop = false;
+        // choose the next sweep; W is only read in here, so that the loop
+        // that rewrites it has the sweep as its one definition of W
+        while (!op && !stop) {
+          if (phase == 0) {
+            if (!rmask) {
+              phase = 1;
+              refresh();
+            } else {
+              idx = uniform(__builtin_ctzll(rmask));
+              rmask &= rmask - 1;
+              ++iters;
+              d = W.column(idx, buf, c, cc);
+              if (d > T(0)) {
+                op = true;
+              } else if (lane == idx) {  // cannot happen for a set that was swept in before
+                st = 0;
+              }
+            }
+          } else if (phase == 1) {
+            const T wrong = (st == 2) ? -yi : ((st == 1) ? yi : -Lim<T>::inf());
+            const T wmax = wave_max(wrong);
+            if (!(readlane(wmax, 0) > T(0))) {
+              phase = 2;
+            } else if (++iters > max_iter) {
+              stop = true;
+            } else {
+              const uint64_t kb = __builtin_amdgcn_ballot_w64(wrong == wmax);
+              idx = kb ? uniform(__builtin_ctzll(kb)) : 0;
+              if (lane == idx) {
+                st = row ? 0 : 3;
+                yi = T(0);
+              }
+              sig = T(-1);
+              d = W.column(idx, buf, c, cc);
+              op = true;
+            }
+          } else {
+            if (!havep) {
+              const T vl = (lt - si) * sl;
+              const T vu = (si - ut) * su;
+              const T viol = (st == 0) ? fmax(vl, vu) : -Lim<T>::inf();
+              const T vmax = wave_max(viol);
+              if (!(readlane(vmax, 0) > tol)) {
+                code = MPCQP_STATUS_OPTIMAL;
+                stop = true;
+              } else {
+                const uint64_t pb = __builtin_amdgcn_ballot_w64(viol == vmax);
+                p = pb ? uniform(__builtin_ctzll(pb)) : 0;
+                sp = readlane(si, p);
+                const T lp = readlane(lt, p), up = readlane(ut, p);
+                mpp = readlane(md, p);
+                side = (sp < lp) ? 1 : 2;
+                tgt = (side == 1) ? lp : up;
+                ysgn = (side == 1) ? T(-1) : T(1);
+                havep = true;
+              }
+            }
+            if (!stop && ++iters > max_iter) stop = true;
+            if (!stop) {
+              T cl;
+              const T wpp = W.template column<true>(p, buf, c, cc, cl);  // cl = W_lane,p
+              const bool dep = !(wpp > dep_tol * fmax(mpp, T(1e-300)));
+              // an active row's multiplier moves toward 0: t = -y / dy (>= 0)
+              const T dy = -cl * ysgn;
+              const bool cand = (st == 2 && dy < T(0)) || (st == 1 && dy > T(0));
+              const T tl = cand ? -yi * fast_rcp(dy) : Lim<T>::inf();
+              const T ti = readlane(wave_min(tl), 0);
+              const uint64_t kb = __builtin_amdgcn_ballot_w64(tl == ti);
+              const int k = kb ? uniform(__builtin_ctzll(kb)) : 0;
+              const T t2 = dep ? Lim<T>::inf() : fabs(sp - tgt) / wpp;
+              if (!(ti < Lim<T>::inf()) && !(t2 < Lim<T>::inf())) {
+                code = MPCQP_STATUS_INFEASIBLE;
+                stop = true;
+              } else if (ti < t2) {  // wave-uniform: a partial step that drops row k
+                if (st == 1 || st == 2) yi = fma(ti, dy, yi);
+                if (lane == k) {
+                  yi = T(0);
+                  st = row ? 0 : 3;
+                }
+                if (!dep) sp = sp - wpp * ysgn * ti;
+                idx = k;
+                sig = T(-1);
+                d = W.column(k, buf, c, cc);
+                op = true;
+              } else if (!(wpp > T(0))) {
+                code = MPCQP_STATUS_NOT_CONVEX;
+                stop = true;
+              } else {
+                idx = p;
+                sig = T(1);
+                d = wpp;
+                add = op = true;
+              }
+            }
+          }
+        }
+        if (stop) break;
+        W.sweep_col(idx, sig, d, c, cc);
+        fresh = false;
+        if (phase == 1) refresh();
+        if (add) {
+          if (lane == p) st = side;
+          refresh();
+          havep = false;
+        }
+      }
+    }
+
+    const bool okc = code == MPCQP_STATUS_OPTIMAL || code == MPCQP_STATUS_MAXITER;
+    if (!okc) {
+      failed = code;
+      yi = T(__builtin_nan(""));
+    }
+    if (a.ys && row) a.ys[tb * mt + lane] = yi;
+    const uint64_t yact = __builtin_amdgcn_ballot_w64(row && yi != T(0));
+    // the applied input from the LDS columns; the plan from the global factors
+    {
+      const int j = lane < nu ? lane : 0;
+      const T uv = poly_epilogue<T>(Kn, Un, nu, j, nx, xl, yi, yact);
+      if (lane < nu) {
+        const T uo = okc ? uv : T(__builtin_nan(""));
+        ul[lane] = uo;
+        a.us[tb * nu + lane] = uo;
+      }
+    }
+    if (a.zs) {
+      for (int j0 = 0; j0 < nz; j0 += kWave) {
+        const int j = j0 + lane;
+        const T zv = poly_epilogue<T>(a.Kt, a.Ut, nz, j < nz ? j : 0, nx, xl, yi, yact);
+        if (j < nz) a.zs[tb * nz + j] = okc ? zv : T(__builtin_nan(""));
+      }
+    }
+    if (lane == 0) a.status[tb] = (code & 0xff) | ((iters & 0xffff) << 8);
+    lds_exchange();
+    // plant: x_{t+1} = A x_t + B u_t (+ w_t)
+    T xn = T(0);
+    if (lane < nx) {
+      for (int j = 0; j < nx; ++j) xn = fma(As[lane * nx + j], xl[j], xn);
+      for (int j = 0; j < nu; ++j) xn = fma(Bs[lane * nu + j], ul[j], xn);
+      if (a.w) xn += wv;
+    }
+    lds_exchange();
+    if (lane < nx) xl[lane] = xn;
+    lds_exchange();
+
+    // the next step's start: cold after a failure (or on request); W reloaded
+    // when the set is empty (free, exact) and rebuilt every kPolyLoopRebuild steps
+    rmask = 0;
+    if (!okc || a.cold) {
+      st = row ? 0 : 3;
+      reload = !fresh;
+    } else {
+      const uint64_t act = __builtin_amdgcn_ballot_w64(st == 1 || st == 2);
+      ++since;
+      if (!act) {
+        reload = !fresh;
+      } else if (since >= kPolyLoopRebuild) {
+        reload = true;
+        rmask = act;
+      } else {
+        reload = false;
+      }
+    }
+  }
+  if (lane < nx) a.xs[((int64_t)a.steps * a.batch + b) * nx + lane] = xl[lane];
+}
+
+template <typename T, int BS>
+static int launch_poly_loop(const PolyLoopArgs<T>& a, hipStream_t st) {
+  const size_t bytes = (size_t)poly_loop_lds(BS, a.mt, a.nx, a.nu) * sizeof(T);
+  if (bytes > 64 * 1024) {
+    set_error("mpcqp_mpc_poly_loop: %zu B of LDS needed, 65536 available", bytes);
+    return MPCQP_ENOTSUP;
+  }
+  hipLaunchKernelGGL((poly_loop_kernel<T, BS>), dim3((unsigned)a.batch), dim3(kWave), bytes, st, a);
+  MPCQP_CHECK_LAUNCH("poly_loop_kernel");
+  return MPCQP_OK;
+}
+
+template <typename T>
+static int poly_loop_t(const PolyLoopArgs<T>& a, hipStream_t st) {
+  switch ((a.mt + 7) / 8) {
+    case 1: return launch_poly_loop<T, 1>(a, st);
+    case 2: return launch_poly_loop<T, 2>(a, st);
+    case 3: return launch_poly_loop<T, 3>(a, st);
+    case 4: return launch_poly_loop<T, 4>(a, st);
+    case 5: return launch_poly_loop<T, 5>(a, st);
+    case 6: return launch_poly_loop<T, 6>(a, st);
+    case 7: return launch_poly_loop<T, 7>(a, st);
+    default: return launch_poly_loop<T, 8>(a, st);
+  }
+}
+
+}  // namespace mpcqp
+
+extern "C" int mpcqp_mpc_poly_loop(int dtype, int batch, int n, int m, int nbox, int nx, int nu,
+                                   int steps, int flags, const void* workspace, const void* E,
+                                   const void* A, const void* Bm, const void* x0,
+                                   int64_t strideX0, const void* hl, const void* hu,
+                                   int64_t strideh, const void* lbz, const void* ubz,
+                                   const void* w, void* xs, void* us, void* zs, void* ys,
+                                   int32_t* status, int max_iter, double tol, void* stream) {
+  using namespace mpcqp;
+  MPCQP_CHECK_ARG(dtype == MPCQP_F64 || dtype == MPCQP_F32, "mpcqp_mpc_poly_loop: bad dtype %d",
+                  dtype);
+  MPCQP_CHECK_ARG(batch >= 0 && n >= 1 && m >= 0 && steps >= 0,
+                  "mpcqp_mpc_poly_loop: bad sizes batch=%d n=%d m=%d steps=%d", batch, n, m, steps);
+  MPCQP_CHECK_ARG(m + (nbox ? n : 0) >= 1 && m + (nbox ? n : 0) <= 64,
+                  "mpcqp_mpc_poly_loop: rows m_total=%d outside [1,64]", m + (nbox ? n : 0));
+  MPCQP_CHECK_ARG(nx >= 1 && nx <= 16 && nu >= 1 && nu <= 16 && nu <= n,
+                  "mpcqp_mpc_poly_loop: nx=%d nu=%d outside 1 <= nx <= 16, 1 <= nu <= min(16, n)",
+                  nx, nu);
+  MPCQP_CHECK_ARG(workspace && A && Bm && x0 && xs && (steps == 0 || (us && status)),
+                  "mpcqp_mpc_poly_loop: workspace, A, B, x0, xs (and us, status for steps > 0) "
+                  "are required");
+  MPCQP_CHECK_ARG(strideX0 >= 0 && strideh >= 0, "mpcqp_mpc_poly_loop: negative stride");
+  MPCQP_CHECK_ARG(!nbox || lbz || ubz, "mpcqp_mpc_poly_loop: nbox set without lbz/ubz");
+  if (batch == 0) return MPCQP_OK;
+  const int mt = m + (nbox ? n : 0);
+  const PolyWs L = poly_ws(dtype_size(dtype), n, mt, nx);
+  const char* base = (const char*)workspace;
+  auto fill = [&](auto& a, auto tp) {
+    using T = decltype(tp);
+    a.batch = batch; a.n = n; a.m = m; a.mt = mt; a.nx = nx; a.nu = nu; a.steps = steps;
+    a.cold = (flags & MPCQP_LOOP_COLD) ? 1 : 0;
+    a.M = (const T*)(base + L.oM); a.Ut = (const T*)(base + L.oUt);
+    a.Kt = (const T*)(base + L.oKt); a.L = (const T*)(base + L.oL);
+    a.flag = (const int32_t*)(base + L.oFlag);
+    a.E = (const T*)E; a.A = (const T*)A; a.B = (const T*)Bm;
+    a.x0 = (const T*)x0; a.sX0 = strideX0;
+    a.hl = (const T*)hl; a.hu = (const T*)hu; a.sh = strideh;
+    a.lbz = nbox ? (const T*)lbz : nullptr; a.ubz = nbox ? (const T*)ubz : nullptr;
+    a.w = (const T*)w;
+    a.xs = (T*)xs; a.us = (T*)us; a.zs = (T*)zs; a.ys = (T*)ys; a.status = status;
+    a.max_iter = max_iter > 0 ? max_iter : 4 * mt + 40;
+    a.tol = tol > 0 ? (T)tol : (dtype == MPCQP_F64 ? (T)1e-12 : (T)1e-6);
+  };
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MPCQP_F64) {
+    PolyLoopArgs<double> a;
+    fill(a, 0.0);
+    return poly_loop_t(a, st);
+  }
+  PolyLoopArgs<float> a;
+  fill(a, 0.0f);
+  return poly_loop_t(a, st);
+}

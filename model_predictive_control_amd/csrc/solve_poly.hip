@@ -28,6 +28,7 @@
 // pivot W_pp (its Schur complement -- zero when p depends on the active rows,
 // in which case a pure dual step drops rows first), dropping row k is a
 // reverse sweep.  Same register-resident sweep machinery as solve_box.hip.
+#include "poly_ws.hpp"
 #include "sym2d.hpp"
 
 namespace mpcqp {
@@ -353,26 +354,6 @@ __global__ void form_l_kernel(const T* G, int m, int n, int mt, int nx, const T*
     acc = Kt[(int64_t)k * n + (r - m)];
   }
   L[e] = acc;
-}
-
-static inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
-
-// Shared factors; independent of the batch size.
-struct PolyWs {
-  int64_t oW, oHinv, oUt, oM, oKt, oL, oFlag, total;
-};
-
-static PolyWs poly_ws(size_t es, int n, int mt, int nx) {
-  PolyWs w;
-  w.oW = 0;
-  w.oHinv = align256(w.oW + (int64_t)n * n * es);
-  w.oUt = align256(w.oHinv + (int64_t)n * n * es);
-  w.oM = align256(w.oUt + (int64_t)mt * n * es);
-  w.oKt = align256(w.oM + (int64_t)mt * (mt + 1) / 2 * es);
-  w.oL = align256(w.oKt + (int64_t)nx * n * es);
-  w.oFlag = align256(w.oL + (int64_t)mt * nx * es);
-  w.total = align256(w.oFlag + 16);
-  return w;
 }
 
 template <typename T, int BS>

@@ -1,0 +1,317 @@
+"""GPU parity: mpcqp_mpc_poly_loop -- the receding-horizon loop of the linear
+MPC with a state box and an input box (sessions 2 and 3), T steps in one
+launch with warm-started active sets -- against oracle.qp.poly_qp on the
+explicitly condensed QP, always evaluated at the device's own recorded state
+xs[t] (tests/_poly_loop_cases.check_episode), so that one differing step
+cannot hide behind two trajectories drifting apart.  The scenarios, and what
+tests/test_poly_loop_host.py certifies about them on the oracle alone, are in
+tests/_poly_loop_cases.py."""
+import numpy as np
+import pytest
+import torch
+
+import _poly_loop_cases as pc
+from model_predictive_control_amd import batched
+from model_predictive_control_amd.closed_loop import lti_mpc_loop
+from model_predictive_control_amd.problems import Problem, Problem3
+from oracle import condense as oc
+
+pytestmark = pytest.mark.gpu
+
+OPT, MAXIT, NOTCVX, INFEAS, NONFIN = 0, 1, 2, 3, 4
+
+
+def _t(a, dev, dt=torch.float64):
+    return None if a is None else torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dev)
+
+
+def _np(r):
+    torch.cuda.synchronize()
+    return {k: (v.double().cpu().numpy() if v.is_floating_point() else v.cpu().numpy())
+            for k, v in r.items() if isinstance(v, torch.Tensor)}
+
+
+def _device_qp(qp, dev, dt=torch.float64):
+    """batched.PolyQP on the factors of a reference LoopQP (the oracle's H, F)."""
+    return batched.PolyQP(_t(oc.pack_lower(qp.H), dev, dt), _t(qp.G, dev, dt) if qp.m else None,
+                          _t(qp.F, dev, dt), _t(qp.lbz, dev, dt) if qp.nbox else None,
+                          _t(qp.ubz, dev, dt) if qp.nbox else None)
+
+
+def _loop(qp, dev, x0, T, *, hl=None, hu=None, plant=None, w=None, dt=torch.float64, dq=None, **kw):
+    dq = dq or _device_qp(qp, dev, dt)
+    A, B = (qp.A, qp.B) if plant is None else plant
+    hl = qp.hl if hl is None else hl
+    hu = qp.hu if hu is None else hu
+    return _np(dq.loop(_t(A, dev, dt), _t(B, dev, dt), _t(x0, dev, dt), T,
+                       _t(hl, dev, dt) if qp.m else None, _t(hu, dev, dt) if qp.m else None,
+                       _t(qp.E, dev, dt), _t(w, dev, dt), plans=True, **kw))
+
+
+def _code(r):
+    return r["status"] & 0xFF
+
+
+def _iters(r):
+    return (r["status"] >> 8) & 0xFFFF
+
+
+# ------------------------------------------------------------------ (c)
+@pytest.mark.parametrize("name", ["Problem", "Problem3"])
+@pytest.mark.parametrize("N", [5, 10])
+def test_session_episodes(dev, name, N):
+    """Sessions 2 and 3 through closed_loop.lti_mpc_loop (device condensing,
+    PolyQP, the loop): every step optimal and the oracle's at the device's
+    state; the trajectory within 1e-8 (1 + |x|) of the oracle's own host loop;
+    the ControllerLog-shaped outputs."""
+    problem = {"Problem": Problem, "Problem3": Problem3}[name]()
+    qp, refs = pc.session_reference(name, N)
+    T, b = pc.T_EPISODE, len(pc.X0_SESSION)
+    out = lti_mpc_loop(problem, pc.X0_SESSION, T, N=N)
+    r = _np(out)
+    assert (_code(r) == OPT).all(), _code(r)
+    assert r["success"].all()
+    zs = r["input_prediction"].reshape(T, b, N)
+    assert np.array_equal(r["xs"][0], pc.X0_SESSION)
+    for i in range(b):
+        pc.check_episode(qp, r["xs"], r["us"], zs, i)
+        hx = refs[i][0]
+        assert np.abs(r["xs"][:, i] - hx).max() < 1e-8 * (1 + np.abs(hx).max()), i
+    assert r["input_prediction"].shape == (T, b, N, 1)
+    assert r["state_prediction"].shape == (T, b, N + 1, 2)
+    assert r["xs"].shape == (T + 1, b, 2) and r["us"].shape == (T, b, 1)
+    assert np.array_equal(r["input_prediction"][:, :, 0], r["us"])
+    assert np.array_equal(r["state_prediction"][:, :, 0], r["xs"][:T])
+    x1 = r["xs"][1:]
+    assert (np.abs(r["state_prediction"][:, :, 1] - x1) <= 1e-12 * (1 + np.abs(x1))).all()
+
+
+def test_session_multipliers(dev):
+    """ys: stationarity with the device's own plan and the sign convention of
+    mpcqp_poly_solve, on the session-2 batch (N = 5)."""
+    qp, _ = pc.session_reference("Problem", 5)
+    r = _loop(qp, dev, pc.X0_SESSION, pc.T_EPISODE, multipliers=True)
+    assert (_code(r) == OPT).all()
+    assert (r["ys"] != 0).any()
+    for i in range(len(pc.X0_SESSION)):
+        for t in range(pc.T_EPISODE):
+            pc.check_multipliers(qp, r["xs"][t, i], r["zs"][t, i], r["ys"][t, i])
+
+
+# ------------------------------------------------------------------ (d)
+@pytest.mark.parametrize("N", [5, 3])
+def test_loss_of_feasibility(dev, N):
+    """Problem(u_min=-2.0): the episodes whose QP becomes empty part-way (the
+    two of N = 5 in one batch, the one of N = 3 in another: the horizon is a
+    property of the launch), each together with a feasible neighbour.  Up to
+    the oracle's failing step every step is optimal and the oracle's; from it
+    on INFEASIBLE with NaN inputs, plans and states; the neighbour is intact."""
+    qp = pc.infeasible_qp(N)
+    cases = [(x0, f) for n_, x0, f in pc.INFEASIBLE_CASES if n_ == N]
+    X0 = np.array([x0 for x0, _ in cases] + [pc.FEASIBLE_NEIGHBOUR])
+    T = pc.T_EPISODE
+    pr = Problem(u_min=-2.0)
+    r = _np(batched.mpc_poly_loop(_t(pr.A, dev), _t(pr.B, dev), _t(pr.Q, dev), _t(pr.R, dev),
+                                  _t(pr.Q, dev), N, _t(X0, dev), _t(pr.x_min, dev),
+                                  _t(pr.x_max, dev), pr.u_min, pr.u_max, T, plans=True))
+    code = _code(r)
+    for i, (_, fail) in enumerate(cases):
+        assert (code[:fail, i] == OPT).all() and (code[fail:, i] == INFEAS).all(), code[:, i]
+        pc.check_episode(qp, r["xs"], r["us"], r["zs"], i, n_steps=fail)
+        assert np.isnan(r["us"][fail:, i]).all() and np.isnan(r["zs"][fail:, i]).all()
+        assert np.isnan(r["xs"][fail + 1:, i]).all() and np.isfinite(r["xs"][:fail + 1, i]).all()
+    i = len(cases)
+    assert (code[:, i] == OPT).all()
+    pc.check_episode(qp, r["xs"], r["us"], r["zs"], i)
+
+
+# ------------------------------------------------------------------ (e)
+@pytest.mark.parametrize("N", [5, 10])
+def test_warm_against_cold(dev, N):
+    """cold=True starts every step from W = M and an empty set: the same
+    status codes and plans; the iteration means are printed."""
+    qp, _ = pc.session_reference("Problem", N)
+    dq = _device_qp(qp, dev)
+    rw = _loop(qp, dev, pc.X0_SESSION, pc.T_EPISODE, dq=dq)
+    rc = _loop(qp, dev, pc.X0_SESSION, pc.T_EPISODE, dq=dq, cold=True)
+    assert np.array_equal(_code(rw), _code(rc)) and (_code(rw) == OPT).all()
+    scale = np.maximum(1.0, np.abs(rc["zs"]).max(axis=-1, keepdims=True))
+    assert (np.abs(rw["zs"] - rc["zs"]) < 1e-9 * scale).all()
+    print(f"N={N}: mean iterations over steps >= 1: warm {_iters(rw)[1:].mean():.2f}, "
+          f"cold {_iters(rc)[1:].mean():.2f}; first step {_iters(rw)[0].mean():.2f}")
+    assert np.array_equal(_iters(rw)[0], _iters(rc)[0])      # the first step is cold in both
+
+
+# ------------------------------------------------------------------ (f)
+def test_drift_200_steps(dev):
+    """W carried over 200 steps with a non-empty active set in 199 of them:
+    every step optimal and the oracle's at the device's state."""
+    qp, w, _ = pc.drift_reference()
+    pr = Problem()
+    r = _np(batched.mpc_poly_loop(_t(pr.A, dev), _t(pr.B, dev), _t(pr.Q, dev), _t(pr.R, dev),
+                                  _t(pr.Q, dev), 5, _t(np.zeros((2, 2)), dev), _t(pr.x_min, dev),
+                                  _t(pr.x_max, dev), pr.u_min, pr.u_max, pc.T_DRIFT, w=_t(w, dev),
+                                  plans=True))
+    assert (_code(r) == OPT).all(), np.unique(_code(r))
+    worst = max(pc.check_episode(qp, r["xs"], r["us"], r["zs"], i, w=w) for i in range(2))
+    print(f"drift: worst relative z error over 200 steps {worst:.2e}, "
+          f"mean iterations {_iters(r).mean():.2f}")
+
+
+# ------------------------------------------------------------------ (g)
+@pytest.mark.parametrize("nx,nu,N", pc.SHAPES)
+def test_every_block_size(dev, nx, nu, N):
+    """ceil(m_total / 8) = 1..8: one kernel instantiation each, padded and
+    unpadded sizes, infinite bounds on the early stages' state rows."""
+    p = pc.shape_problem(nx, nu, N)
+    qp = p["qp"]
+    r = _loop(qp, dev, p["x0"], pc.SHAPE_T, multipliers=True)
+    assert (_code(r) == OPT).all(), _code(r)
+    for i in range(pc.SHAPE_B):
+        pc.check_episode(qp, r["xs"], r["us"], r["zs"], i)
+        for t in range(pc.SHAPE_T):
+            pc.check_multipliers(qp, r["xs"][t, i], r["zs"][t, i], r["ys"][t, i])
+
+
+def test_config4_rows_on_the_plan(dev):
+    """BASELINE config 4 as a loop: 40 fixed rows G z <= hu (E = NULL, no box,
+    hl absent), n = 200, nx = 12, nu = 4."""
+    p = pc.config4_problem()
+    qp = p["qp"]
+    r = _loop(qp, dev, p["x0"], pc.SHAPE_T)
+    assert (_code(r) == OPT).all(), _code(r)
+    assert (_iters(r) > 0).any()
+    for i in range(pc.SHAPE_B):
+        pc.check_episode(qp, r["xs"], r["us"], r["zs"], i)
+
+
+# ------------------------------------------------------------------ (h)
+def test_edges_steps_and_batches(dev):
+    qp, refs = pc.session_reference("Problem", 5)
+    r0 = _loop(qp, dev, pc.X0_SESSION[:3], 0)
+    assert r0["xs"].shape == (1, 3, 2) and np.array_equal(r0["xs"][0], pc.X0_SESSION[:3])
+    assert r0["us"].shape == (0, 3, 1) and r0["status"].shape == (0, 3)
+    for b in (1, 3):
+        r = _loop(qp, dev, pc.X0_SESSION[1:1 + b], pc.T_EPISODE)
+        assert (_code(r) == OPT).all()
+        for i in range(b):
+            pc.check_episode(qp, r["xs"], r["us"], r["zs"], i)
+
+
+def test_edges_nonfinite_and_infeasible(dev):
+    """NaN / Inf in x0: NONFINITE for that instance only; a NaN in w at step 2:
+    NONFINITE from step 2; hl > hu on a row: INFEASIBLE at every step;
+    NONFINITE goes before INFEASIBLE when both hold."""
+    qp, _ = pc.session_reference("Problem", 5)
+    T = 6
+    X0 = pc.X0_SESSION[[0, 1, 2, 3, 4, 5]].copy()
+    X0[1, 1] = np.nan
+    X0[3, 0] = np.inf
+    X0[5, 0] = np.nan
+    hl = np.tile(qp.hl, (6, 1))
+    hu = np.tile(qp.hu, (6, 1))
+    hl[4, 3] = hu[4, 3] + 1.0          # empty row: INFEASIBLE
+    hl[5, 7] = hu[5, 7] + 1.0          # with a NaN state: NONFINITE first
+    w = np.zeros((T, 6, 2))
+    w[2, 2, 1] = np.nan
+    r = _loop(qp, dev, X0, T, hl=hl, hu=hu, w=w, multipliers=True)
+    code = _code(r)
+    want = [[OPT] * T, [NONFIN] * T, [OPT] * 2 + [NONFIN] * (T - 2), [NONFIN] * T, [INFEAS] * T,
+            [NONFIN] * T]
+    assert code.T.tolist() == want, code.T
+    pc.check_episode(qp, r["xs"], r["us"], r["zs"], 0, w=w)
+    pc.check_episode(qp, r["xs"], r["us"], r["zs"], 2, w=w, n_steps=2)
+    assert np.array_equal(r["xs"][0], X0, equal_nan=True)
+    for i, first in ((1, 0), (2, 2), (3, 0), (4, 0), (5, 0)):
+        assert np.isnan(r["us"][first:, i]).all() and np.isnan(r["zs"][first:, i]).all(), i
+        assert np.isnan(r["ys"][first:, i]).all() and np.isnan(r["xs"][first + 1:, i]).all(), i
+
+
+def test_edges_max_iter(dev):
+    """max_iter = 2: only OPTIMAL and MAXITER occur, every plan is finite, the
+    optimal steps are the oracle's, and the episode runs all T steps."""
+    qp, _ = pc.session_reference("Problem", 5)
+    X0 = pc.X0_SESSION[[0, 1, 4, 5, 6]]
+    r = _loop(qp, dev, X0, pc.T_EPISODE, max_iter=2)
+    code = _code(r)
+    assert np.isin(code, (OPT, MAXIT)).all(), code
+    assert (code == MAXIT).any() and (code == OPT).any()
+    assert (_iters(r) <= 3).all()
+    assert np.isfinite(r["zs"]).all() and np.isfinite(r["xs"]).all()
+    assert r["xs"].shape[0] == pc.T_EPISODE + 1
+    for i in range(len(X0)):
+        pc.check_episode(qp, r["xs"], r["us"], r["zs"], i,
+                         z_steps=set(np.nonzero(code[:, i] == OPT)[0].tolist()))
+
+
+def test_edges_plant_mismatch(dev):
+    """plant=(1.05 A, B): the controller keeps its model, the states follow
+    the plant's own matrices."""
+    pr = Problem()
+    qp, _ = pc.session_reference("Problem", 5)
+    plant = (1.05 * pr.A, pr.B.astype(float))
+    X0 = pc.X0_SESSION[[0, 2, 6]]
+    r = _np(batched.mpc_poly_loop(_t(pr.A, dev), _t(pr.B, dev), _t(pr.Q, dev), _t(pr.R, dev),
+                                  _t(pr.Q, dev), 5, _t(X0, dev), _t(pr.x_min, dev),
+                                  _t(pr.x_max, dev), pr.u_min, pr.u_max, 8,
+                                  plant=(_t(plant[0], dev), _t(plant[1], dev)), plans=True))
+    code = _code(r)
+    for i in range(3):
+        ok = int(np.argmax(code[:, i] != OPT)) if (code[:, i] != OPT).any() else 8
+        assert ok >= 2, code[:, i]
+        pc.check_episode(qp, r["xs"], r["us"], r["zs"], i, plant=plant, n_steps=ok)
+    assert (code[:, 2] == OPT).all()
+
+
+def test_edges_shared_against_broadcast_bounds(dev):
+    """hl/hu shared (stride 0) against the same bounds per instance: bitwise."""
+    qp, _ = pc.session_reference("Problem", 5)
+    b = len(pc.X0_SESSION)
+    rs = _loop(qp, dev, pc.X0_SESSION, pc.T_EPISODE)
+    rb = _loop(qp, dev, pc.X0_SESSION, pc.T_EPISODE, hl=np.tile(qp.hl, (b, 1)),
+               hu=np.tile(qp.hu, (b, 1)))
+    for k in ("xs", "us", "zs", "status"):
+        assert np.array_equal(rs[k], rb[k]), k
+
+
+def test_python_surface_validation(dev):
+    qp, _ = pc.session_reference("Problem", 5)
+    dq = _device_qp(qp, dev)
+    A, B, x0 = _t(qp.A, dev), _t(qp.B, dev), _t(pc.X0_SESSION, dev)
+    with pytest.raises(ValueError):
+        dq.loop(A, B, x0[:, :1], 3)
+    with pytest.raises(ValueError):
+        dq.loop(A, B, x0, 3, hl=_t(qp.hl[:4], dev))
+    with pytest.raises(ValueError):
+        dq.loop(A, B, x0, 3, w=_t(np.zeros((2, 7, 2)), dev))
+    with pytest.raises(ValueError):
+        dq.loop(A[:1], B, x0, 3)
+    with pytest.raises(ValueError):
+        batched.PolyQP(_t(oc.pack_lower(qp.H), dev), lbz=-1.0).loop(A, B, x0, 3)     # no F
+
+
+# ------------------------------------------------------------------ (i)
+# The largest relative error of zs measured over the three fp32 episodes
+# below against the fp64 oracle on the fp32-rounded data ("Poly
+# loop"), and the bound: 10 x that, floor 2e-4 (the floor of _tol32 in
+# tests/test_gpu_loop_box.py); the factor covers other seeds.
+FP32_MEASURED = 2.1e-6          # 1.4e-7, 2.1e-6, 1.9e-6 for the three shapes
+FP32_BOUND = max(2e-4, 10 * FP32_MEASURED)
+
+
+@pytest.mark.parametrize("nx,nu,N", [(2, 1, 5), (2, 2, 8), (4, 2, 7)])
+def test_fp32(dev, nx, nu, N):
+    p = pc.shape_problem(nx, nu, N)
+    q = p["qp"]
+    f32 = lambda a: np.asarray(a, np.float32).astype(np.float64)  # noqa: E731
+    q32 = pc.LoopQP(f32(q.H), f32(q.F), f32(q.G), f32(q.E), f32(q.hl), f32(q.hu), f32(q.lbz),
+                    f32(q.ubz), f32(q.A), f32(q.B))
+    x0 = f32(p["x0"])
+    T = 5
+    r = _loop(q32, dev, x0, T, dt=torch.float32)
+    assert (_code(r) == OPT).all(), _code(r)
+    worst = 0.0
+    for i in range(pc.SHAPE_B):
+        worst = max(worst, pc.check_episode(q32, r["xs"], r["us"], r["zs"], i, tol=FP32_BOUND,
+                                            fp32=True))
+    print(f"fp32 ({nx}, {nu}, {N}): worst relative z error {worst:.3e} (bound {FP32_BOUND:.1e})")

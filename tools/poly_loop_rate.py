@@ -1,0 +1,165 @@
+"""Closed-loop rate of the state-constrained linear MPC: the one-launch device
+loop (mpcqp_mpc_poly_loop, warm and cold) against the per-step path that
+exists without it -- T x (PolyQP.solve with out= + the row-bound update
+hl - Phi x_t, hu - Phi x_t + the torch plant), captured in one HIP graph.
+
+  python tools/poly_loop_rate.py [--config4] [--batch 4096] [--steps 50]
+                                 [--repeats 20] [--json PATH]
+
+Default: the session-2 Problem (session_2/problem.py:4-33), N = 5, Qf = Q, x0
+uniform in p in [-100, 0], v in [-15, 25].  --config4: nx = 12, nu = 4, N = 50,
+40 fixed rows on the plan (BASELINE config 4; no row-bound update).  Times are
+HIP events around each path, warm-up first, median of the repeats.  Prints one
+JSON line (and appends it to --json).
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from model_predictive_control_amd import batched  # noqa: E402
+from model_predictive_control_amd.problems import Problem  # noqa: E402
+
+
+def _median_ms(fn, warmup, repeats):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return float(np.median(ts)), float(np.min(ts))
+
+
+def _session2(batch, dev):
+    pr = Problem()
+    t = lambda a: torch.as_tensor(np.asarray(a, float), dtype=torch.float64, device=dev)  # noqa: E731
+    N = pr.N
+    cd = batched.condense(t(pr.A), t(pr.B), t(pr.Q), t(pr.R), t(pr.Q), N,
+                          outputs=("H", "F", "Gam", "Phi"))
+    cd = {k: v[0] for k, v in cd.items()}
+    n = N * pr.n_input
+    qp = batched.PolyQP(cd["H"], cd["Gam"], cd["F"], torch.full((n,), pr.u_min, dtype=torch.float64),
+                        torch.full((n,), pr.u_max, dtype=torch.float64), device=dev)
+    rng = np.random.default_rng(0)
+    x0 = np.stack([rng.uniform(-100, 0, batch), rng.uniform(-15, 25, batch)], axis=1)
+    return dict(qp=qp, A=t(pr.A), B=t(pr.B), x0=t(x0), hl=t(np.tile(pr.x_min, N)),
+                hu=t(np.tile(pr.x_max, N)), E=cd["Phi"], name="session2_N5")
+
+
+def _config4(batch, dev):
+    nx, nu, N, m = 12, 4, 50, 40
+    rng = np.random.default_rng(nx * 100 + N)
+    t = lambda a: torch.as_tensor(np.asarray(a, float), dtype=torch.float64, device=dev)  # noqa: E731
+    U, _ = np.linalg.qr(rng.normal(size=(nx, nx)))
+    A = (U * rng.uniform(0.5, 0.98, nx)) @ U.T
+    B = rng.normal(size=(nx, nu)) / np.sqrt(nx)
+    cd = batched.condense(t(A), t(B), t(np.eye(nx)), t(0.1 * np.eye(nu)), t(np.eye(nx)), N,
+                          outputs=("H", "F"))
+    G = rng.normal(size=(m, N * nu))
+    hu = rng.uniform(0.5, 1.5, size=m)
+    qp = batched.PolyQP(cd["H"][0], t(G), cd["F"][0])
+    x0 = rng.normal(size=(batch, nx)) * 3
+    return dict(qp=qp, A=t(A), B=t(B), x0=t(x0), hl=None, hu=t(hu), E=None, name="config4")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config4", action="store_true")
+    ap.add_argument("--batch", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    assert a.repeats >= 10
+    dev = torch.device("cuda:0")
+    p = (_config4 if a.config4 else _session2)(a.batch, dev)
+    qp, A, B, x0, hl, hu, E = (p[k] for k in ("qp", "A", "B", "x0", "hl", "hu", "E"))
+    b, T, nx, nu, n = a.batch, a.steps, A.shape[0], B.shape[1], qp.n
+    f64 = dict(dtype=torch.float64, device=dev)
+
+    # ---- the one-launch loop, warm and cold
+    outs = {}
+    for cold in (False, True):
+        o = dict(xs=torch.empty((T + 1, b, nx), **f64), us=torch.empty((T, b, nu), **f64),
+                 status=torch.empty((T, b), dtype=torch.int32, device=dev))
+        outs[cold] = (o, lambda o=o, cold=cold: qp.loop(A, B, x0, T, hl, hu, E, cold=cold, out=o))
+    ms_warm = _median_ms(outs[False][1], a.warmup, a.repeats)
+    ms_cold = _median_ms(outs[True][1], a.warmup, a.repeats)
+
+    # ---- the per-step path, T steps in one HIP graph
+    xs = torch.empty((T + 1, b, nx), **f64)
+    zs = torch.empty((T, b, n), **f64)
+    y = torch.empty((b, qp.mt), **f64)
+    st = torch.empty((T, b), dtype=torch.int32, device=dev)
+    hlt = None if hl is None or E is None else torch.empty((b, qp.m), **f64)
+    hut = None if hu is None or E is None else torch.empty((b, qp.m), **f64)
+    Et = None if E is None else E.T.contiguous()
+    At, Bt = A.T.contiguous(), B.T.contiguous()
+    tmp = torch.empty((b, nx), **f64)
+
+    def episode():
+        xs[0].copy_(x0)
+        for t in range(T):
+            x = xs[t]
+            if Et is not None:
+                torch.addmm(hl, x, Et, alpha=-1.0, out=hlt)
+                torch.addmm(hu, x, Et, alpha=-1.0, out=hut)
+                qp.solve(x, None, hlt, hut, out=(zs[t], y, st[t]))
+            else:
+                qp.solve(x, None, hl, hu, out=(zs[t], y, st[t]))
+            torch.mm(x, At, out=tmp)
+            torch.addmm(tmp, zs[t, :, :nu], Bt, out=xs[t + 1])
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        episode()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        episode()
+    ms_step = _median_ms(graph.replay, a.warmup, a.repeats)
+    torch.cuda.synchronize()
+
+    ow, oc_ = outs[False][0], outs[True][0]
+    code_w, code_s = ow["status"] & 0xFF, st & 0xFF
+    both = ((code_w == 0) & (code_s == 0)).all(dim=0)       # instances optimal throughout in both
+    diff = (ow["xs"][:, both] - xs[:, both]).abs().max().item() if both.any() else float("nan")
+    it = lambda s: ((s[1:] >> 8) & 0xFFFF).double().mean().item()  # noqa: E731
+    rate = lambda ms: b * T / (ms * 1e-3)  # noqa: E731
+    res = dict(tool="poly_loop_rate", problem=p["name"], batch=b, steps=T, n=n, m_total=qp.mt,
+               loop_warm_ms=ms_warm[0], loop_cold_ms=ms_cold[0], per_step_graph_ms=ms_step[0],
+               loop_warm_steps_per_s=rate(ms_warm[0]), loop_cold_steps_per_s=rate(ms_cold[0]),
+               per_step_graph_steps_per_s=rate(ms_step[0]),
+               speedup_warm_vs_per_step=ms_step[0] / ms_warm[0],
+               iters_warm_mean=it(ow["status"]), iters_cold_mean=it(oc_["status"]),
+               iters_per_step_path_mean=it(st),
+               optimal_fraction_loop=(code_w == 0).double().mean().item(),
+               optimal_fraction_per_step=(code_s == 0).double().mean().item(),
+               max_abs_x_diff_loop_vs_per_step=diff, repeats=a.repeats,
+               min_ms=dict(warm=ms_warm[1], cold=ms_cold[1], per_step=ms_step[1]))
+    line = json.dumps(res)
+    print(line)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "a") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
