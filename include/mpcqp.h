@@ -625,6 +625,43 @@ int mpcqp_mpc_poly_loop(int dtype, int batch, int n, int m, int nbox, int nx, in
                         int max_iter, double tol, void* stream);
 
 /*
+ * mpcqp_mpc_poly_loop with soft rows: the same loop, arguments and outputs,
+ * where row i < m of G carries an exact penalty on a slack shared by its two
+ * sides (rho_i >= 0 linear, sigma_i > 0 quadratic weight); per step
+ *   min over z, eps >= 0:  1/2 z'Hz + (F x_t)'z
+ *                          + sum_i ( rho_i eps_i + 1/2 sigma_i eps_i^2 )
+ *   s.t.  hl_i - (E x_t)_i - eps_i <= (G z)_i <= hu_i - (E x_t)_i + eps_i
+ * and the hard rows and the input box as before.  The plan obeys a soft row
+ * exactly whenever it can (it equals the hard loop's wherever rho_i exceeds
+ * the hard problem's |y_i|), violates it as little as the penalty allows when
+ * it cannot, and the episode goes on: a soft row never makes a step
+ * INFEASIBLE (a hard row or the box still can).  Softening costs no extra
+ * row: a soft row has a third state, soft-active (|y_i| > rho_i, row value =
+ * bound +- (|y_i| - rho_i)/sigma_i), handled inside the dual active set.
+ * rho, sigma: m each, shared by the batch.  rho[i] = +inf makes row i hard;
+ * sigma[i] is read only where rho[i] is finite; rho[i] = 0 is the pure
+ * quadratic penalty.  The box rows are always hard.  rho = NULL is exactly
+ * mpcqp_mpc_poly_loop.  A penalty that is NaN or negative, or a sigma outside
+ * (0, inf) on a row with finite rho, gives NONFINITE on every step.
+ * eps (optional, steps x batch x m): the slacks, eps_i = max(0, |y_i| -
+ * rho_i)/sigma_i; NaN on a failed step.  ys holds the full multipliers.
+ * Status: as mpcqp_mpc_poly_loop, plus MPCQP_STATUS_SOFTENED on a step that
+ * ends with a soft-active row (an eps_i > 0); regime switches of a row count
+ * as iterations in bits 8..23 and against max_iter like any other trip.
+ * Not supported: soft rows in mpcqp_poly_solve, the box loop, per-instance
+ * penalties, sigma = 0 (the pure L1 penalty).
+ */
+#define MPCQP_STATUS_SOFTENED (1 << 26)
+int mpcqp_mpc_poly_loop_soft(int dtype, int batch, int n, int m, int nbox, int nx, int nu,
+                             int steps, int flags, const void* workspace, const void* E,
+                             const void* A, const void* Bm, const void* x0, int64_t strideX0,
+                             const void* hl, const void* hu, int64_t strideh,
+                             const void* lbz, const void* ubz, const void* w,
+                             const void* rho, const void* sigma,
+                             void* xs, void* us, void* zs, void* ys, void* eps,
+                             int32_t* status, int max_iter, double tol, void* stream);
+
+/*
  * Batched finite-horizon Riccati recursion, FHC.py:51-61:
  *   K_k = -(R + B'P B)^{-1} B'P A,  P_k = Q + A'P A + A'P B K_k,  P_N = Pf
  * Outputs in the reference's order (lists reversed: K[0] is the first-stage

@@ -24,6 +24,7 @@ STRICT = 4
 LOOP_COLD = 16  # mpcqp_mpc_poly_loop: every step from an empty active set
 STATUS_POLISHED = 1 << 24
 STATUS_UNREFINED = 1 << 25
+STATUS_SOFTENED = 1 << 26  # mpcqp_mpc_poly_loop_soft: the step ends with a soft-active row
 SQP_DONE = 1
 SQP_EXACT = 2
 SQP_FAIL = 4
@@ -91,6 +92,8 @@ SIGNATURES = {
     "mpcqp_mpc_box_loop": (_i, [_i] * 6 + [_vp, _i64] * 7 + [_vp] * 3 + [_vp, _i, _d, _vp]),
     "mpcqp_mpc_poly_loop": (_i, [_i] * 9 + [_vp] * 5 + [_i64, _vp, _vp, _i64] + [_vp] * 8 +
                             [_i, _d, _vp]),
+    "mpcqp_mpc_poly_loop_soft": (_i, [_i] * 9 + [_vp] * 5 + [_i64, _vp, _vp, _i64] + [_vp] * 11 +
+                                 [_i, _d, _vp]),
     "mpcqp_mpc_qp_profile": (_i, [_i]),
     "mpcqp_mpc_qp_stage_ms": (_i, [ctypes.POINTER(ctypes.c_float)]),
     "mpcqp_bicycle_hessian": (_i, [_i, _i, _i, _d, ctypes.POINTER(ctypes.c_double), _i, _vp, _vp,

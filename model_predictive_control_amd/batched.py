@@ -587,7 +587,8 @@ class PolyQP:
 
     def loop(self, A, B, x0, steps: int, hl=None, hu=None, E=None, w=None, *,
              plans: bool = False, multipliers: bool = False, cold: bool = False,
-             max_iter: int = 0, tol: float = 0.0, out: dict | None = None) -> dict:
+             max_iter: int = 0, tol: float = 0.0, out: dict | None = None,
+             soft: tuple | None = None, slacks: bool = False) -> dict:
         """The receding-horizon loop on this object's factors, ``steps`` steps
         in one launch (include/mpcqp.h ``mpcqp_mpc_poly_loop``): per step
         z_t = argmin 1/2 z'Hz + (F x_t)'z over hl - E x_t <= G z <= hu - E x_t,
@@ -597,7 +598,15 @@ class PolyQP:
         (m,) | (b, m); E (m, nx) or None; w (steps, b, nx) or None.  Each step
         starts from the previous step's active set unless ``cold``.  Returns
         xs (steps+1, b, nx), us (steps, b, nu), status (steps, b), with
-        ``plans`` zs (steps, b, n), with ``multipliers`` ys (steps, b, m_total)."""
+        ``plans`` zs (steps, b, n), with ``multipliers`` ys (steps, b, m_total).
+
+        ``soft=(rho, sigma)`` (scalars or (m,), shared by the batch) softens
+        the rows of G with the exact penalty rho_i eps_i + 1/2 sigma_i eps_i^2
+        on a slack eps_i >= 0 shared by the row's two sides
+        (``mpcqp_mpc_poly_loop_soft``); rho_i = inf keeps row i hard, the
+        input box always is.  A step that ends with a slack > 0 carries
+        ``STATUS_SOFTENED`` in its status word; with ``slacks`` eps (steps, b,
+        m) is returned too."""
         dt, dev, n, m, nx = self.dtype, self.device, self.n, self.m, self.nx
         if nx == 0:
             raise ValueError("PolyQP.loop needs the x0 -> gradient map F at construction")
@@ -630,9 +639,26 @@ class PolyQP:
         w = _dev(w, dt, dev)
         if w is not None and tuple(w.shape) != (T, batch, nx):
             raise ValueError(f"w must be ({T}, {batch}, {nx}), got {tuple(w.shape)}")
+        rho = sigma = None
+        if soft is not None:
+            if not isinstance(soft, (tuple, list)) or len(soft) != 2:
+                raise ValueError("soft must be a pair (rho, sigma)")
+            pen = []
+            for name, v in zip(("rho", "sigma"), soft):
+                v = torch.as_tensor(v, dtype=dt, device=dev)
+                if v.ndim == 0:
+                    v = v.expand(m)
+                if tuple(v.shape) != (m,):
+                    raise ValueError(f"soft {name} must be a scalar or ({m},), got {tuple(v.shape)}")
+                pen.append(v.contiguous())
+            rho, sigma = pen
+        elif slacks:
+            raise ValueError("slacks=True needs soft=(rho, sigma)")
         o = dict(out or {})
         shapes = dict(xs=((T + 1, batch, nx), dt), us=((T, batch, nu), dt),
                       status=((T, batch), torch.int32))
+        if slacks:
+            shapes["eps"] = ((T, batch, m), dt)
         if plans:
             shapes["zs"] = ((T, batch, n), dt)
         if multipliers:
@@ -642,6 +668,15 @@ class PolyQP:
                 o[k] = torch.empty(shp, dtype=kd, device=dev)
             elif tuple(o[k].shape) != shp or o[k].dtype != kd or not o[k].is_contiguous():
                 raise ValueError(f"out[{k!r}] must be a contiguous {kd} tensor of shape {shp}")
+        if rho is not None and m > 0:
+            rc = _lib().mpcqp_mpc_poly_loop_soft(
+                _code(dt), batch, n, m, self.nbox, nx, nu, T, nat.LOOP_COLD if cold else 0,
+                _ptr(self.ws), _ptr(E), _ptr(A), _ptr(B), _ptr(x0), nx, _ptr(hl), _ptr(hu), sh,
+                _ptr(self.lbz), _ptr(self.ubz), _ptr(w), _ptr(rho), _ptr(sigma), _ptr(o["xs"]),
+                _ptr(o["us"]), _ptr(o.get("zs")), _ptr(o.get("ys")), _ptr(o.get("eps")),
+                _ptr(o["status"]), int(max_iter), float(tol), _stream())
+            nat.check(rc, "mpcqp_mpc_poly_loop_soft")
+            return o
         rc = _lib().mpcqp_mpc_poly_loop(
             _code(dt), batch, n, m, self.nbox, nx, nu, T, nat.LOOP_COLD if cold else 0,
             _ptr(self.ws), _ptr(E), _ptr(A), _ptr(B), _ptr(x0), nx, _ptr(hl), _ptr(hu), sh,
@@ -655,7 +690,7 @@ class PolyQP:
 def mpc_poly_loop(A, B, Q, R, Qf, N: int, x0, xlo=None, xhi=None, lb=None, ub=None,
                   steps: int = 1, *, plant=None, w=None, plans: bool = False,
                   multipliers: bool = False, cold: bool = False, max_iter: int = 0,
-                  tol: float = 0.0) -> dict:
+                  tol: float = 0.0, soft: tuple | None = None, slacks: bool = False) -> dict:
     """The receding-horizon loop of the linear MPC with a state box on
     x_1..x_N and an input box (sessions 2 and 3, session_2/problem.py:4-33), on
     the device in one launch.  The shared model (A, B) is condensed once (H, F,
@@ -663,8 +698,11 @@ def mpc_poly_loop(A, B, Q, R, Qf, N: int, x0, xlo=None, xhi=None, lb=None, ub=No
     Phi x_t of a ``PolyQP`` (G = Gam, E = Phi), lb/ub (scalar, (nu,) or
     (N*nu,)) its input box, and ``PolyQP.loop`` runs the episode.
     ``plant=(A_p, B_p)`` simulates another plant than the controller's model.
-    x0 (b, nx); xlo/xhi (nx,) or None.  Returns the dict of ``PolyQP.loop``
-    plus ``condensed`` (H, F, Gam, Phi of the model, unbatched)."""
+    x0 (b, nx); xlo/xhi (nx,) or None.  ``soft=(rho, sigma)`` softens the
+    state box (``PolyQP.loop``): each a scalar, (nx,) per state component or
+    (N*nx,) per row; ``slacks`` returns eps (steps, b, N*nx).  Returns the
+    dict of ``PolyQP.loop`` plus ``condensed`` (H, F, Gam, Phi of the model,
+    unbatched)."""
     dt = A.dtype if isinstance(A, torch.Tensor) else torch.float64
     dev = A.device if isinstance(A, torch.Tensor) else torch.device("cuda")
     A, B = _dev(A, dt, dev), _dev(B, dt, dev)
@@ -691,8 +729,15 @@ def mpc_poly_loop(A, B, Q, R, Qf, N: int, x0, xlo=None, xhi=None, lb=None, ub=No
     qp = PolyQP(cd["H"], cd["Gam"] if rows else None, cd["F"], stage_bound(lb, nu, "lb"),
                 stage_bound(ub, nu, "ub"))
     Ap, Bp = (A, B) if plant is None else plant
+    if soft is not None:
+        if not isinstance(soft, (tuple, list)) or len(soft) != 2:
+            raise ValueError("soft must be a pair (rho, sigma)")
+        if not rows:
+            raise ValueError("soft needs a state box (xlo or xhi)")
+        soft = (stage_bound(soft[0], nx, "soft rho"), stage_bound(soft[1], nx, "soft sigma"))
     o = qp.loop(Ap, Bp, x0, steps, hl, hu, cd["Phi"] if rows else None, w, plans=plans,
-                multipliers=multipliers, cold=cold, max_iter=max_iter, tol=tol)
+                multipliers=multipliers, cold=cold, max_iter=max_iter, tol=tol, soft=soft,
+                slacks=slacks)
     o["condensed"] = cd
     return o
 

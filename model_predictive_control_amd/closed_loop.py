@@ -204,7 +204,8 @@ def lti_box_mpc_loop(A, B, Q, R, Qf, N: int, X0, lb, ub, steps: int) -> dict:
 
 
 def lti_mpc_loop(problem, X0, steps: int, *, N: int | None = None, Qf=None, plant=None, w=None,
-                 cold: bool = False, max_iter: int = 0, tol: float = 0.0) -> dict:
+                 cold: bool = False, max_iter: int = 0, tol: float = 0.0,
+                 soft: tuple | None = None) -> dict:
     """The receding-horizon loop of the state- and input-constrained linear MPC
     of sessions 2 and 3 (session_2/problem.py:4-33) on a linear plant, all
     ``steps`` in one launch (``batched.mpc_poly_loop``).  ``problem`` is a
@@ -215,7 +216,11 @@ def lti_mpc_loop(problem, X0, steps: int, *, N: int | None = None, Qf=None, plan
     nx) is a plant disturbance.  X0 (b, nx) -> the ControllerLog fields
     (session_2/log.py:8-12) batched: success (T, b) (solver_success),
     input_prediction (T, b, N, nu), state_prediction (T, b, N+1, nx) = [x_t;
-    Phi x_t + Gam z_t]; and xs (T+1, b, nx), us (T, b, nu), status, iters."""
+    Phi x_t + Gam z_t]; and xs (T+1, b, nx), us (T, b, nu), status, iters.
+    ``soft=(rho, sigma)`` (each a scalar, (nx,) or (N*nx,)) softens the state
+    box with an exact penalty (``batched.mpc_poly_loop``) and adds slack (T, b,
+    N, nx), by which the predicted state may leave the box, and softened (T,
+    b), whether any does; success stays "the step's code is 0"."""
     dev = torch.device("cuda")
     t = lambda a: None if a is None else torch.as_tensor(a, dtype=torch.float64, device=dev)  # noqa: E731
     if isinstance(problem, dict):
@@ -236,12 +241,17 @@ def lti_mpc_loop(problem, X0, steps: int, *, N: int | None = None, Qf=None, plan
     if plant is not None:
         plant = (t(plant[0]), t(plant[1]))
     r = batched.mpc_poly_loop(A, B, Q, R, Qf, N, X0, t(xlo), t(xhi), lb, ub, T, plant=plant,
-                              w=t(w), plans=True, cold=cold, max_iter=max_iter, tol=tol)
+                              w=t(w), plans=True, cold=cold, max_iter=max_iter, tol=tol,
+                              soft=soft, slacks=soft is not None)
     cd = r["condensed"]
     xs, zs = r["xs"], r["zs"]
     pred = xs[:T] @ cd["Phi"].T + zs @ cd["Gam"].T                 # (T, b, N*nx)
     state_prediction = torch.cat([xs[:T].unsqueeze(2), pred.reshape(T, b, N, nx)], dim=2)
-    return {"xs": xs, "us": r["us"], "status": r["status"],
-            "success": batched.status_code(r["status"]) == 0,
-            "iters": batched.status_iters(r["status"]),
-            "input_prediction": zs.reshape(T, b, N, nu), "state_prediction": state_prediction}
+    out = {"xs": xs, "us": r["us"], "status": r["status"],
+           "success": batched.status_code(r["status"]) == 0,
+           "iters": batched.status_iters(r["status"]),
+           "input_prediction": zs.reshape(T, b, N, nu), "state_prediction": state_prediction}
+    if soft is not None:
+        out["slack"] = r["eps"].reshape(T, b, N, nx)
+        out["softened"] = (r["status"] & nat.STATUS_SOFTENED) != 0
+    return out

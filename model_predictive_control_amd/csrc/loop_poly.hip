@@ -35,6 +35,11 @@
 // register set, as in dual_range_kernel.  Every trip counts against max_iter,
 // except the rebuild sweeps, which a bit mask of at most mt rows bounds; every
 // exit test is written so that a NaN operand ends the loop.
+//
+// mpcqp_mpc_poly_loop_soft is the SOFT instantiation of the same kernel: rows
+// with an exact penalty on a shared slack instead of a hard bound, as a third
+// row state inside the same active set (see poly_loop_kernel).
+// The hard instantiation compiles to what it was without the variant.
 #include "poly_ws.hpp"
 #include "sym2d.hpp"
 
@@ -67,6 +72,16 @@ struct PolyLoopArgs {
   T tol;
 };
 
+// mpcqp_mpc_poly_loop_soft: the per-row penalties and the slack output
+template <typename T>
+struct PolyLoopSoftArgs : PolyLoopArgs<T> {
+  const T* rho;                // m, +inf = hard row
+  const T* sigma;              // m, read where rho is finite
+  T* eps;                      // steps x batch x m or null
+};
+template <typename T, bool SOFT>
+using PolyLoopArgsOf = std::conditional_t<SOFT, PolyLoopSoftArgs<T>, PolyLoopArgs<T>>;
+
 // LDS elements of the loop kernel: Sym2D scratch, the mat-vec partials, packed
 // M, L' and E' (nx x NMAX each, transposed: lane = row reads conflict-free),
 // A, B, the first nu columns of Ut (NMAX x nu) and Kt (nx x nu), x_t, u_t.
@@ -94,8 +109,16 @@ __device__ __forceinline__ T poly_epilogue(const T* Kt, const T* Ut, int64_t ld,
 
 // st: 0 inactive, 1 at lower, 2 at upper, 3 padding row; row-indexed vectors
 // one row per lane, as in dual_range_kernel.
-template <typename T, int BS>
-__global__ __launch_bounds__(64) void poly_loop_kernel(PolyLoopArgs<T> a) {
+//
+// SOFT: rows < m with a finite rho are soft (exact penalty rho eps + 1/2 sigma
+// eps^2 on a slack shared by the row's two sides).  Such a row has a third
+// state, "soft-active" (|y| > rho, row value = bound + sgn (|y| - rho)/sigma),
+// held as the regime bit sr next to st; a soft-active row is an ordinary
+// active row of the problem with M_ii + 1/sigma on its diagonal and the bound
+// moved by -sgn rho/sigma, so W is SWEEP_A of that matrix and a regime switch
+// of an active row is a rank-one update of W (Sym2D::update_col).
+template <typename T, int BS, bool SOFT>
+__global__ __launch_bounds__(64) void poly_loop_kernel(PolyLoopArgsOf<T, SOFT> a) {
   using S2 = Sym2D<T, BS>;
   constexpr int NMAX = S2::NMAX;
   static_assert(NMAX <= kWave, "one row per lane");
@@ -153,6 +176,21 @@ __global__ __launch_bounds__(64) void poly_loop_kernel(PolyLoopArgs<T> a) {
     md = Ps[lane * (lane + 1) / 2 + lane];
   }
   bool nf0 = row && (li != li || ui != ui);
+  // penalties: rho (+inf on hard rows), 1/sigma (0 on hard rows), and the
+  // regime of an active row: sr = soft-active
+  T rho = Lim<T>::inf(), isg = T(0);
+  bool sr = false;
+  if constexpr (SOFT) {
+    if (lane < m) {
+      rho = a.rho[lane];
+      nf0 |= !(rho >= T(0));
+      if (rho < Lim<T>::inf()) {
+        const T sg = a.sigma[lane];
+        nf0 |= !(sg > T(0) && sg < Lim<T>::inf());
+        isg = T(1) / sg;
+      }
+    }
+  }
   for (int e = lane; e < P; e += kWave) nf0 |= !finite(Ps[e]);
   const bool badbox =
       row && (!(li <= ui) || li == Lim<T>::inf() || ui == -Lim<T>::inf());
@@ -217,7 +255,10 @@ __global__ __launch_bounds__(64) void poly_loop_kernel(PolyLoopArgs<T> a) {
       // active: y = -v, s = bound;  inactive: s = s0 - v
       auto refresh = [&]() {
         const bool act = st == 1 || st == 2;
-        const T bnd = (st == 1) ? lt : ut;
+        T bnd = (st == 1) ? lt : ut;
+        if constexpr (SOFT) {
+          if (sr) bnd -= ((st == 1) ? -rho : rho) * isg;
+        }
         const T v = matvec_lane_lds<T, BS>(W, act ? s0 - bnd : T(0), buf, part);
         yi = act ? -v : T(0);
         si = act ? bnd : s0 - v;
@@ -230,10 +271,15 @@ __global__ __launch_bounds__(64) void poly_loop_kernel(PolyLoopArgs<T> a) {
       bool havep = false;
       int p = 0, side = 0;
       T sp = T(0), tgt = T(0), ysgn = T(0), mpp = T(1);
+      // SOFT, for the entering row p: its penalties, |y_p| so far, and whether
+      // it has passed rho (then sp is its row value less the slack)
+      T rhop = Lim<T>::inf(), isgp = T(0), yp = T(0);
+      bool psoft = false;
       code = MPCQP_STATUS_MAXITER;
       while (true) {
         int idx = 0;
-        T sig = T(1), d = T(1);
+        T sig = T(1), d = T(1), dd = T(0);
+        bool r1 = false;
         T c[BS], cc[BS];
         bool add = false, op = false, stop = false;
         // choose the next sweep; W is only read in here, so that the loop
@@ -248,14 +294,20 @@ __global__ __launch_bounds__(64) void poly_loop_kernel(PolyLoopArgs<T> a) {
               rmask &= rmask - 1;
               ++iters;
               d = W.column(idx, buf, c, cc);
+              if constexpr (SOFT) d += readlane(sr ? isg : T(0), idx);
               if (d > T(0)) {
                 op = true;
               } else if (lane == idx) {  // cannot happen for a set that was swept in before
                 st = 0;
+                sr = false;
               }
             }
           } else if (phase == 1) {
-            const T wrong = (st == 2) ? -yi : ((st == 1) ? yi : -Lim<T>::inf());
+            T wrong = (st == 2) ? -yi : ((st == 1) ? yi : -Lim<T>::inf());
+            if constexpr (SOFT) {
+              // ... or whose |y| is on the wrong side of rho for its regime
+              if (st == 1 || st == 2) wrong = sr ? rho + wrong : fmax(wrong, -wrong - rho);
+            }
             const T wmax = wave_max(wrong);
             if (!(readlane(wmax, 0) > T(0))) {
               phase = 2;
@@ -264,9 +316,11 @@ __global__ __launch_bounds__(64) void poly_loop_kernel(PolyLoopArgs<T> a) {
             } else {
               const uint64_t kb = __builtin_amdgcn_ballot_w64(wrong == wmax);
               idx = kb ? uniform(__builtin_ctzll(kb)) : 0;
+              if constexpr (SOFT) dd = readlane(sr ? -isg : T(0), idx);
               if (lane == idx) {
                 st = row ? 0 : 3;
                 yi = T(0);
+                sr = false;
               }
               sig = T(-1);
               d = W.column(idx, buf, c, cc);
@@ -291,53 +345,161 @@ __global__ __launch_bounds__(64) void poly_loop_kernel(PolyLoopArgs<T> a) {
                 tgt = (side == 1) ? lp : up;
                 ysgn = (side == 1) ? T(-1) : T(1);
                 havep = true;
+                if constexpr (SOFT) {
+                  rhop = readlane(rho, p);
+                  isgp = readlane(isg, p);
+                  yp = T(0);
+                  psoft = !(rhop > T(0));
+                }
               }
             }
             if (!stop && ++iters > max_iter) stop = true;
             if (!stop) {
-              T cl;
-              const T wpp = W.template column<true>(p, buf, c, cc, cl);  // cl = W_lane,p
-              const bool dep = !(wpp > dep_tol * fmax(mpp, T(1e-300)));
-              // an active row's multiplier moves toward 0: t = -y / dy (>= 0)
-              const T dy = -cl * ysgn;
-              const bool cand = (st == 2 && dy < T(0)) || (st == 1 && dy > T(0));
-              const T tl = cand ? -yi * fast_rcp(dy) : Lim<T>::inf();
-              const T ti = readlane(wave_min(tl), 0);
-              const uint64_t kb = __builtin_amdgcn_ballot_w64(tl == ti);
-              const int k = kb ? uniform(__builtin_ctzll(kb)) : 0;
-              const T t2 = dep ? Lim<T>::inf() : fabs(sp - tgt) / wpp;
-              if (!(ti < Lim<T>::inf()) && !(t2 < Lim<T>::inf())) {
-                code = MPCQP_STATUS_INFEASIBLE;
-                stop = true;
-              } else if (ti < t2) {  // wave-uniform: a partial step that drops row k
-                if (st == 1 || st == 2) yi = fma(ti, dy, yi);
-                if (lane == k) {
-                  yi = T(0);
-                  st = row ? 0 : 3;
+              if constexpr (SOFT) {
+                T cl;
+                const T wpp0 = W.template column<true>(p, buf, c, cc, cl);  // cl = W_lane,p
+                // past rho the row's pivot carries its 1/sigma
+                const T wpp = psoft ? wpp0 + isgp : wpp0;
+                const T mref = psoft ? mpp + isgp : mpp;
+                const bool dep = !(wpp > dep_tol * fmax(mref, T(1e-300)));
+                // an active row's multiplier moves toward 0: t = -y / dy (>= 0)
+                const T dy = -cl * ysgn;
+                // Along the ray of a dependent row p only the rows that p depends on
+                // move: cl = 0 elsewhere, exactly so while W is M swept, but left as
+                // rounding noise by the 1/sigma updates, and no bound on the step
+                // hides an event at -y / noise.  With a soft-active row in the set,
+                // a row moves if its share |cl| sqrt(M_ii) of row p's norm passes
+                // dep_tol.
+                const bool ray = dep && __any(sr);
+                const bool moves =
+                    !ray || cl * cl * md > dep_tol * dep_tol * fmax(mref, T(1e-300));
+                const bool cand = moves && ((st == 2 && dy < T(0)) || (st == 1 && dy > T(0)));
+                T tl = cand ? -yi * fast_rcp(dy) : Lim<T>::inf();
+                int kind = 0;  // of this lane's event: 0 drop, 1 to soft-active, 2 back to hard-active
+                const T ady = fabs(dy);
+                if (cand && sr) {  // |y| shrinks to rho first
+                  tl = fmax(fabs(yi) - rho, T(0)) * fast_rcp(ady);
+                  kind = 2;
+                } else if (!cand && moves && (st == 1 || st == 2) && !sr && rho < Lim<T>::inf() &&
+                           ady > T(0)) {  // |y| grows to rho
+                  tl = fmax(rho - fabs(yi), T(0)) * fast_rcp(ady);
+                  kind = 1;
                 }
-                if (!dep) sp = sp - wpp * ysgn * ti;
-                idx = k;
-                sig = T(-1);
-                d = W.column(k, buf, c, cc);
-                op = true;
-              } else if (!(wpp > T(0))) {
-                code = MPCQP_STATUS_NOT_CONVEX;
-                stop = true;
+                const T ti = readlane(wave_min(tl), 0);
+                const uint64_t kb = __builtin_amdgcn_ballot_w64(tl == ti);
+                const int k = kb ? uniform(__builtin_ctzll(kb)) : 0;
+                const T t2 = dep ? Lim<T>::inf() : fabs(sp - tgt) / wpp;
+                // |y_p| reaches rho_p before the row reaches its bound
+                const T t3 = !psoft ? rhop - yp : Lim<T>::inf();
+                if (!(ti < Lim<T>::inf()) && !(t2 < Lim<T>::inf()) && !(t3 < Lim<T>::inf())) {
+                  code = MPCQP_STATUS_INFEASIBLE;
+                  stop = true;
+                } else if (ti < t2 && ti < t3) {  // wave-uniform: a partial step to row k's event
+                  if (st == 1 || st == 2) yi = fma(ti, dy, yi);
+                  if (!dep) sp = sp - wpp * ysgn * ti;
+                  const int kk = uniform(readlane(kind, k));
+                  idx = k;
+                  d = W.column(k, buf, c, cc);
+                  if (kk == 0) {
+                    if (lane == k) {
+                      yi = T(0);
+                      st = row ? 0 : 3;
+                    }
+                    sig = T(-1);
+                  } else {  // regime switch of row k at |y_k| = rho_k: M_kk -+ 1/sigma_k
+                    const T dl = readlane(kk == 1 ? isg : -isg, k);
+                    const T den = T(1) - dl * d;  // >= 1 towards soft, in [0, 1] back to hard
+                    if (den > dep_tol) {
+                      if (lane == k) {
+                        yi = (st == 1) ? -rho : rho;
+                        sr = kk == 1;
+                      }
+                      d = dl / den;
+                      r1 = true;
+                    } else {
+                      // as a hard row k depends on the rest of the set (a velocity row
+                      // next to the input bound that fixes it): it cannot stay.  It
+                      // leaves, and the step starts over from the repair with the set
+                      // that is left.
+                      if (lane == k) {
+                        yi = T(0);
+                        st = row ? 0 : 3;
+                        sr = false;
+                      }
+                      dd = dl;
+                      sig = T(-1);
+                      phase = 1;
+                      havep = false;
+                    }
+                  }
+                  yp += ti;
+                  op = true;
+                } else if (t3 < t2) {  // row p goes on as a soft row; W is not touched
+                  if (st == 1 || st == 2) yi = fma(t3, dy, yi);
+                  if (!dep) sp = sp - wpp * ysgn * t3;
+                  yp = rhop;
+                  psoft = true;
+                } else if (!(wpp > T(0))) {
+                  code = MPCQP_STATUS_NOT_CONVEX;
+                  stop = true;
+                } else {
+                  idx = p;
+                  sig = T(1);
+                  d = wpp;
+                  add = op = true;
+                }
               } else {
-                idx = p;
-                sig = T(1);
-                d = wpp;
-                add = op = true;
+                T cl;
+                const T wpp = W.template column<true>(p, buf, c, cc, cl);  // cl = W_lane,p
+                const bool dep = !(wpp > dep_tol * fmax(mpp, T(1e-300)));
+                // an active row's multiplier moves toward 0: t = -y / dy (>= 0)
+                const T dy = -cl * ysgn;
+                const bool cand = (st == 2 && dy < T(0)) || (st == 1 && dy > T(0));
+                const T tl = cand ? -yi * fast_rcp(dy) : Lim<T>::inf();
+                const T ti = readlane(wave_min(tl), 0);
+                const uint64_t kb = __builtin_amdgcn_ballot_w64(tl == ti);
+                const int k = kb ? uniform(__builtin_ctzll(kb)) : 0;
+                const T t2 = dep ? Lim<T>::inf() : fabs(sp - tgt) / wpp;
+                if (!(ti < Lim<T>::inf()) && !(t2 < Lim<T>::inf())) {
+                  code = MPCQP_STATUS_INFEASIBLE;
+                  stop = true;
+                } else if (ti < t2) {  // wave-uniform: a partial step that drops row k
+                  if (st == 1 || st == 2) yi = fma(ti, dy, yi);
+                  if (lane == k) {
+                    yi = T(0);
+                    st = row ? 0 : 3;
+                  }
+                  if (!dep) sp = sp - wpp * ysgn * ti;
+                  idx = k;
+                  sig = T(-1);
+                  d = W.column(k, buf, c, cc);
+                  op = true;
+                } else if (!(wpp > T(0))) {
+                  code = MPCQP_STATUS_NOT_CONVEX;
+                  stop = true;
+                } else {
+                  idx = p;
+                  sig = T(1);
+                  d = wpp;
+                  add = op = true;
+                }
               }
             }
           }
         }
         if (stop) break;
-        W.sweep_col(idx, sig, d, c, cc);
+        if constexpr (SOFT) {
+          W.update_col(idx, sig, d, r1, dd, c, cc);
+        } else {
+          W.sweep_col(idx, sig, d, c, cc);
+        }
         fresh = false;
         if (phase == 1) refresh();
         if (add) {
-          if (lane == p) st = side;
+          if (lane == p) {
+            st = side;
+            sr = psoft;
+          }
           refresh();
           havep = false;
         }
@@ -368,7 +530,15 @@ __global__ __launch_bounds__(64) void poly_loop_kernel(PolyLoopArgs<T> a) {
         if (j < nz) a.zs[tb * nz + j] = okc ? zv : T(__builtin_nan(""));
       }
     }
-    if (lane == 0) a.status[tb] = (code & 0xff) | ((iters & 0xffff) << 8);
+    int word = (code & 0xff) | ((iters & 0xffff) << 8);
+    if constexpr (SOFT) {
+      // the slack of a soft-active row; bit 26 when the step ends with one
+      T ev = (sr && (st == 1 || st == 2)) ? fmax((fabs(yi) - rho) * isg, T(0)) : T(0);
+      if (!okc) ev = T(__builtin_nan(""));
+      if (__any(ev > T(0))) word |= MPCQP_STATUS_SOFTENED;
+      if (a.eps && lane < m) a.eps[tb * m + lane] = ev;
+    }
+    if (lane == 0) a.status[tb] = word;
     lds_exchange();
     // plant: x_{t+1} = A x_t + B u_t (+ w_t)
     T xn = T(0);
@@ -386,6 +556,7 @@ __global__ __launch_bounds__(64) void poly_loop_kernel(PolyLoopArgs<T> a) {
     rmask = 0;
     if (!okc || a.cold) {
       st = row ? 0 : 3;
+      sr = false;
       reload = !fresh;
     } else {
       const uint64_t act = __builtin_amdgcn_ballot_w64(st == 1 || st == 2);
@@ -403,56 +574,53 @@ __global__ __launch_bounds__(64) void poly_loop_kernel(PolyLoopArgs<T> a) {
   if (lane < nx) a.xs[((int64_t)a.steps * a.batch + b) * nx + lane] = xl[lane];
 }
 
-template <typename T, int BS>
-static int launch_poly_loop(const PolyLoopArgs<T>& a, hipStream_t st) {
+template <typename T, int BS, bool SOFT>
+static int launch_poly_loop(const PolyLoopArgsOf<T, SOFT>& a, hipStream_t st) {
   const size_t bytes = (size_t)poly_loop_lds(BS, a.mt, a.nx, a.nu) * sizeof(T);
   if (bytes > 64 * 1024) {
     set_error("mpcqp_mpc_poly_loop: %zu B of LDS needed, 65536 available", bytes);
     return MPCQP_ENOTSUP;
   }
-  hipLaunchKernelGGL((poly_loop_kernel<T, BS>), dim3((unsigned)a.batch), dim3(kWave), bytes, st, a);
+  hipLaunchKernelGGL((poly_loop_kernel<T, BS, SOFT>), dim3((unsigned)a.batch), dim3(kWave), bytes,
+                     st, a);
   MPCQP_CHECK_LAUNCH("poly_loop_kernel");
   return MPCQP_OK;
 }
 
-template <typename T>
-static int poly_loop_t(const PolyLoopArgs<T>& a, hipStream_t st) {
+template <typename T, bool SOFT>
+static int poly_loop_t(const PolyLoopArgsOf<T, SOFT>& a, hipStream_t st) {
   switch ((a.mt + 7) / 8) {
-    case 1: return launch_poly_loop<T, 1>(a, st);
-    case 2: return launch_poly_loop<T, 2>(a, st);
-    case 3: return launch_poly_loop<T, 3>(a, st);
-    case 4: return launch_poly_loop<T, 4>(a, st);
-    case 5: return launch_poly_loop<T, 5>(a, st);
-    case 6: return launch_poly_loop<T, 6>(a, st);
-    case 7: return launch_poly_loop<T, 7>(a, st);
-    default: return launch_poly_loop<T, 8>(a, st);
+    case 1: return launch_poly_loop<T, 1, SOFT>(a, st);
+    case 2: return launch_poly_loop<T, 2, SOFT>(a, st);
+    case 3: return launch_poly_loop<T, 3, SOFT>(a, st);
+    case 4: return launch_poly_loop<T, 4, SOFT>(a, st);
+    case 5: return launch_poly_loop<T, 5, SOFT>(a, st);
+    case 6: return launch_poly_loop<T, 6, SOFT>(a, st);
+    case 7: return launch_poly_loop<T, 7, SOFT>(a, st);
+    default: return launch_poly_loop<T, 8, SOFT>(a, st);
   }
 }
 
-}  // namespace mpcqp
-
-extern "C" int mpcqp_mpc_poly_loop(int dtype, int batch, int n, int m, int nbox, int nx, int nu,
-                                   int steps, int flags, const void* workspace, const void* E,
-                                   const void* A, const void* Bm, const void* x0,
-                                   int64_t strideX0, const void* hl, const void* hu,
-                                   int64_t strideh, const void* lbz, const void* ubz,
-                                   const void* w, void* xs, void* us, void* zs, void* ys,
-                                   int32_t* status, int max_iter, double tol, void* stream) {
-  using namespace mpcqp;
-  MPCQP_CHECK_ARG(dtype == MPCQP_F64 || dtype == MPCQP_F32, "mpcqp_mpc_poly_loop: bad dtype %d",
-                  dtype);
+// Both entry points: rho == nullptr is the hard loop.
+static int poly_loop_entry(const char* who, int dtype, int batch, int n, int m, int nbox, int nx,
+                           int nu, int steps, int flags, const void* workspace, const void* E,
+                           const void* A, const void* Bm, const void* x0, int64_t strideX0,
+                           const void* hl, const void* hu, int64_t strideh, const void* lbz,
+                           const void* ubz, const void* w, const void* rho, const void* sigma,
+                           void* xs, void* us, void* zs, void* ys, void* eps, int32_t* status,
+                           int max_iter, double tol, void* stream) {
+  MPCQP_CHECK_ARG(dtype == MPCQP_F64 || dtype == MPCQP_F32, "%s: bad dtype %d", who, dtype);
   MPCQP_CHECK_ARG(batch >= 0 && n >= 1 && m >= 0 && steps >= 0,
-                  "mpcqp_mpc_poly_loop: bad sizes batch=%d n=%d m=%d steps=%d", batch, n, m, steps);
+                  "%s: bad sizes batch=%d n=%d m=%d steps=%d", who, batch, n, m, steps);
   MPCQP_CHECK_ARG(m + (nbox ? n : 0) >= 1 && m + (nbox ? n : 0) <= 64,
-                  "mpcqp_mpc_poly_loop: rows m_total=%d outside [1,64]", m + (nbox ? n : 0));
+                  "%s: rows m_total=%d outside [1,64]", who, m + (nbox ? n : 0));
   MPCQP_CHECK_ARG(nx >= 1 && nx <= 16 && nu >= 1 && nu <= 16 && nu <= n,
-                  "mpcqp_mpc_poly_loop: nx=%d nu=%d outside 1 <= nx <= 16, 1 <= nu <= min(16, n)",
-                  nx, nu);
+                  "%s: nx=%d nu=%d outside 1 <= nx <= 16, 1 <= nu <= min(16, n)", who, nx, nu);
   MPCQP_CHECK_ARG(workspace && A && Bm && x0 && xs && (steps == 0 || (us && status)),
-                  "mpcqp_mpc_poly_loop: workspace, A, B, x0, xs (and us, status for steps > 0) "
-                  "are required");
-  MPCQP_CHECK_ARG(strideX0 >= 0 && strideh >= 0, "mpcqp_mpc_poly_loop: negative stride");
-  MPCQP_CHECK_ARG(!nbox || lbz || ubz, "mpcqp_mpc_poly_loop: nbox set without lbz/ubz");
+                  "%s: workspace, A, B, x0, xs (and us, status for steps > 0) are required", who);
+  MPCQP_CHECK_ARG(strideX0 >= 0 && strideh >= 0, "%s: negative stride", who);
+  MPCQP_CHECK_ARG(!nbox || lbz || ubz, "%s: nbox set without lbz/ubz", who);
+  MPCQP_CHECK_ARG(!rho || sigma, "%s: rho given without sigma", who);
   if (batch == 0) return MPCQP_OK;
   const int mt = m + (nbox ? n : 0);
   const PolyWs L = poly_ws(dtype_size(dtype), n, mt, nx);
@@ -473,13 +641,48 @@ extern "C" int mpcqp_mpc_poly_loop(int dtype, int batch, int n, int m, int nbox,
     a.max_iter = max_iter > 0 ? max_iter : 4 * mt + 40;
     a.tol = tol > 0 ? (T)tol : (dtype == MPCQP_F64 ? (T)1e-12 : (T)1e-6);
   };
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == MPCQP_F64) {
-    PolyLoopArgs<double> a;
-    fill(a, 0.0);
-    return poly_loop_t(a, st);
-  }
-  PolyLoopArgs<float> a;
-  fill(a, 0.0f);
-  return poly_loop_t(a, st);
+  auto run = [&](auto tp) {
+    using T = decltype(tp);
+    hipStream_t st = (hipStream_t)stream;
+    if (rho) {
+      PolyLoopSoftArgs<T> a;
+      fill(a, tp);
+      a.rho = (const T*)rho; a.sigma = (const T*)sigma; a.eps = (T*)eps;
+      return poly_loop_t<T, true>(a, st);
+    }
+    PolyLoopArgs<T> a;
+    fill(a, tp);
+    return poly_loop_t<T, false>(a, st);
+  };
+  return dtype == MPCQP_F64 ? run(0.0) : run(0.0f);
+}
+
+}  // namespace mpcqp
+
+extern "C" int mpcqp_mpc_poly_loop(int dtype, int batch, int n, int m, int nbox, int nx, int nu,
+                                   int steps, int flags, const void* workspace, const void* E,
+                                   const void* A, const void* Bm, const void* x0,
+                                   int64_t strideX0, const void* hl, const void* hu,
+                                   int64_t strideh, const void* lbz, const void* ubz,
+                                   const void* w, void* xs, void* us, void* zs, void* ys,
+                                   int32_t* status, int max_iter, double tol, void* stream) {
+  return mpcqp::poly_loop_entry("mpcqp_mpc_poly_loop", dtype, batch, n, m, nbox, nx, nu, steps,
+                                flags, workspace, E, A, Bm, x0, strideX0, hl, hu, strideh, lbz, ubz,
+                                w, nullptr, nullptr, xs, us, zs, ys, nullptr, status, max_iter, tol,
+                                stream);
+}
+
+extern "C" int mpcqp_mpc_poly_loop_soft(int dtype, int batch, int n, int m, int nbox, int nx,
+                                        int nu, int steps, int flags, const void* workspace,
+                                        const void* E, const void* A, const void* Bm,
+                                        const void* x0, int64_t strideX0, const void* hl,
+                                        const void* hu, int64_t strideh, const void* lbz,
+                                        const void* ubz, const void* w, const void* rho,
+                                        const void* sigma, void* xs, void* us, void* zs, void* ys,
+                                        void* eps, int32_t* status, int max_iter, double tol,
+                                        void* stream) {
+  return mpcqp::poly_loop_entry("mpcqp_mpc_poly_loop_soft", dtype, batch, n, m, nbox, nx, nu,
+                                steps, flags, workspace, E, A, Bm, x0, strideX0, hl, hu, strideh,
+                                lbz, ubz, w, rho, sigma, xs, us, zs, ys, eps, status, max_iter, tol,
+                                stream);
 }

@@ -236,6 +236,45 @@ struct Sym2D {
     patch_col<0>(kc, bj == kb, k, rd, sigma, ar);
   }
 
+  // M_kk += dd on the lane that holds it (uniform switch over k's offset)
+  template <int R>
+  __device__ __forceinline__ void bump_diag(int kc, bool on, T dd) {
+    if constexpr (R < BS) {
+      if (kc == R) {
+        m[R][R] = on ? m[R][R] + dd : m[R][R];
+        asm volatile("; s2dg %0" ::"n"(R));
+      } else {
+        bump_diag<R + 1>(kc, on, dd);
+      }
+    }
+  }
+  // sweep_col for a matrix whose diagonal carries terms that come and go
+  // (M_kk + delta_k on some rows), still one definition of M:
+  //   r1 = false: the sweep on pivot k with d = M_kk (a delta of an unswept
+  //     k is added to d by the caller: no other element depends on it), then
+  //     M_kk += dd (takes the delta off a pivot that has just left the set);
+  //   r1 = true: no sweep; k is in the swept set and its M_kk changes by
+  //     delta, which is the rank-one update M += d col col' with
+  //     d = delta / (1 - delta M_kk) on the whole swept matrix, pivot row
+  //     and column included.  sigma and dd are not used.
+  // r1 is wave-uniform.
+  __device__ __forceinline__ void update_col(int k, T sigma, T d, bool r1, T dd,
+                                             const T (&colr)[BS], const T (&colc)[BS]) {
+    k = __builtin_amdgcn_readfirstlane(k);
+    const int kb = k / BS, kc = k - kb * BS;
+    const T rd = r1 ? -d : fast_rcp(d);
+    T ar[BS];
+#pragma unroll
+    for (int r = 0; r < BS; ++r) ar[r] = colr[r] * rd;
+#pragma unroll
+    for (int r = 0; r < BS; ++r)
+#pragma unroll
+      for (int c = 0; c < BS; ++c) m[r][c] = fma(-ar[r], colc[c], m[r][c]);
+    patch_row<0>(kc, !r1 && bi == kb, k, rd, sigma * rd, colc);
+    patch_col<0>(kc, !r1 && bj == kb, k, rd, sigma, ar);
+    bump_diag<0>(kc, !r1 && bi == kb && bj == kb, dd);
+  }
+
   // Fetch column k and sweep on it.  Returns the pivot M_kk.
   __device__ __forceinline__ T sweep(int k, T sigma, T* buf) {
     T colr[BS], colc[BS];

@@ -11,8 +11,24 @@ uniform in p in [-100, 0], v in [-15, 25].  --config4: nx = 12, nu = 4, N = 50,
 40 fixed rows on the plan (BASELINE config 4; no row-bound update).  Times are
 HIP events around each path, warm-up first, median of the repeats.  Prints one
 JSON line (and appends it to --json).
+
+  python tools/poly_loop_rate.py --soft [--config4 | --horizon N] [--ab-lib OTHER.so] ...
+
+--soft measures the soft loop (mpcqp_mpc_poly_loop_soft) instead:
+  1. the hard warm loop of this build, and with --ab-lib the same call into
+     another build of the library (the parent commit's), timed alternately in
+     --rounds rounds of --repeats launches: the median of each round, so that
+     the two builds can be compared against each build's own spread;
+  2. (session-2 batch only) the soft loop with rho = 2000, sigma = 1 on the
+     same batch (the hard loop's iterations wherever the hard QP is feasible)
+     and with rho = inf (the hard loop's iterations everywhere): the price of
+     the variant;
+  3. (session-2 batch only) Problem(u_min=-2.0), x0 drawn the same way: the
+     soft loop with (50, 1) -- rate, share of softened steps, iterations --
+     and the hard loop on it -- rate, share of dead (instance, step) pairs.
 """
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -24,6 +40,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from model_predictive_control_amd import _native as nat  # noqa: E402
 from model_predictive_control_amd import batched  # noqa: E402
 from model_predictive_control_amd.problems import Problem  # noqa: E402
 
@@ -43,8 +60,10 @@ def _median_ms(fn, warmup, repeats):
     return float(np.median(ts)), float(np.min(ts))
 
 
-def _session2(batch, dev):
-    pr = Problem()
+def _session2(batch, dev, pr=None, N=None):
+    pr = pr or Problem()
+    if N:
+        pr.N = N
     t = lambda a: torch.as_tensor(np.asarray(a, float), dtype=torch.float64, device=dev)  # noqa: E731
     N = pr.N
     cd = batched.condense(t(pr.A), t(pr.B), t(pr.Q), t(pr.R), t(pr.Q), N,
@@ -56,7 +75,7 @@ def _session2(batch, dev):
     rng = np.random.default_rng(0)
     x0 = np.stack([rng.uniform(-100, 0, batch), rng.uniform(-15, 25, batch)], axis=1)
     return dict(qp=qp, A=t(pr.A), B=t(pr.B), x0=t(x0), hl=t(np.tile(pr.x_min, N)),
-                hu=t(np.tile(pr.x_max, N)), E=cd["Phi"], name="session2_N5")
+                hu=t(np.tile(pr.x_max, N)), E=cd["Phi"], name=f"session2_N{N}")
 
 
 def _config4(batch, dev):
@@ -75,9 +94,116 @@ def _config4(batch, dev):
     return dict(qp=qp, A=t(A), B=t(B), x0=t(x0), hl=None, hu=t(hu), E=None, name="config4")
 
 
+def _hard_loop_call(lib, p, T, o):
+    """The hard warm loop as a direct call into ``lib`` (this build's library or
+    another build's; the workspace layout is that of mpcqp_poly_setup)."""
+    qp, A, B, x0, hl, hu, E = (p[k] for k in ("qp", "A", "B", "x0", "hl", "hu", "E"))
+    ptr = batched._ptr
+    fn = lib.mpcqp_mpc_poly_loop
+    fn.restype, fn.argtypes = nat.SIGNATURES["mpcqp_mpc_poly_loop"]
+    args = (nat.F64, x0.shape[0], qp.n, qp.m, qp.nbox, A.shape[0], B.shape[1], T, 0, ptr(qp.ws),
+            ptr(E), ptr(A), ptr(B), ptr(x0), A.shape[0], ptr(hl), ptr(hu), 0, ptr(qp.lbz),
+            ptr(qp.ubz), None, ptr(o["xs"]), ptr(o["us"]), None, None, ptr(o["status"]), 0, 0.0,
+            batched._stream())
+
+    def call():
+        rc = fn(*args)
+        assert rc == 0, rc
+    return call
+
+
+def _outs(b, T, nx, nu, dev):
+    f64 = dict(dtype=torch.float64, device=dev)
+    return dict(xs=torch.empty((T + 1, b, nx), **f64), us=torch.empty((T, b, nu), **f64),
+                status=torch.empty((T, b), dtype=torch.int32, device=dev))
+
+
+def _stats(o):
+    st = o["status"]
+    code = st & 0xFF
+    it = ((st >> 8) & 0xFFFF).double()
+    return dict(iters_mean=it[1:].mean().item(),
+                iters_per_episode_max=it.sum(dim=0).max().item(),
+                optimal_fraction=(code == 0).double().mean().item(),
+                dead_fraction=(code > 1).double().mean().item(),
+                softened_fraction=((st & nat.STATUS_SOFTENED) != 0).double().mean().item())
+
+
+def soft_mode(a, dev):
+    b, T = a.batch, a.steps
+    rate = lambda ms: b * T / (ms * 1e-3)  # noqa: E731
+    p = _config4(b, dev) if a.config4 else _session2(b, dev, N=a.horizon)
+    nx, nu = p["A"].shape[0], p["B"].shape[1]
+    res = dict(tool="poly_loop_rate", mode="soft", problem=p["name"], batch=b, steps=T,
+               m_total=p["qp"].mt, repeats=a.repeats, rounds=a.rounds)
+
+    # 1. the hard warm loop: this build, and another build alternately
+    libs = {"this": nat.load()}
+    if a.ab_lib:
+        libs["other"] = ctypes.CDLL(os.path.abspath(a.ab_lib))
+    outs = {k: _outs(b, T, nx, nu, dev) for k in libs}
+    calls = {k: _hard_loop_call(lib, p, T, outs[k]) for k, lib in libs.items()}
+    med = {k: [] for k in libs}
+    for _ in range(a.rounds):
+        for k in libs:
+            med[k].append(_median_ms(calls[k], a.warmup, a.repeats)[0])
+    for k in libs:
+        res[f"hard_{k}_round_medians_ms"] = med[k]
+        res[f"hard_{k}_ms"] = float(np.median(med[k]))
+        res[f"hard_{k}_steps_per_s"] = rate(float(np.median(med[k])))
+    if a.ab_lib:
+        res["hard_outputs_equal"] = all(torch.equal(outs["this"][k], outs["other"][k])
+                                        if k == "status" else
+                                        torch.equal(outs["this"][k].isnan(), outs["other"][k].isnan())
+                                        and bool((outs["this"][k].nan_to_num() ==
+                                                  outs["other"][k].nan_to_num()).all())
+                                        for k in ("xs", "us", "status"))
+    res["hard"] = _stats(outs["this"])
+
+    if not a.config4:
+        def soft_run(pp, rho, sigma):
+            # a direct call like the hard loop's, so that both are timed alike
+            o = _outs(b, T, nx, nu, dev)
+            qq, m = pp["qp"], pp["qp"].m
+            pen = (torch.full((m,), rho, dtype=torch.float64, device=dev),
+                   torch.full((m,), sigma, dtype=torch.float64, device=dev))
+            ptr = batched._ptr
+            lib = nat.load()
+            args = (nat.F64, b, qq.n, m, qq.nbox, nx, nu, T, 0, ptr(qq.ws), ptr(pp["E"]),
+                    ptr(pp["A"]), ptr(pp["B"]), ptr(pp["x0"]), nx, ptr(pp["hl"]), ptr(pp["hu"]), 0,
+                    ptr(qq.lbz), ptr(qq.ubz), None, ptr(pen[0]), ptr(pen[1]), ptr(o["xs"]),
+                    ptr(o["us"]), None, None, None, ptr(o["status"]), 0, 0.0, batched._stream())
+
+            def fn():
+                rc = lib.mpcqp_mpc_poly_loop_soft(*args)
+                assert rc == 0, rc
+            ms = _median_ms(fn, a.warmup, a.repeats)[0]
+            return dict(ms=ms, steps_per_s=rate(ms), **_stats(o))
+
+        # 2. the price of the variant: same batch, same iterations
+        s2 = soft_run(p, 2000.0, 1.0)
+        s2["ms_over_hard"] = s2["ms"] / res["hard_this_ms"]
+        res["soft_rho2000"] = s2
+        # ... and with every row hard (rho = inf): the hard loop's very trips
+        s0 = soft_run(p, float("inf"), 1.0)
+        s0["ms_over_hard"] = s0["ms"] / res["hard_this_ms"]
+        res["soft_rho_inf"] = s0
+        # 3. a batch that loses feasibility
+        q = _session2(b, dev, Problem(u_min=-2.0), N=a.horizon)
+        oh = _outs(b, T, nx, nu, dev)
+        ms_h = _median_ms(_hard_loop_call(nat.load(), q, T, oh), a.warmup, a.repeats)[0]
+        res["umin2_hard"] = dict(ms=ms_h, steps_per_s=rate(ms_h), **_stats(oh))
+        res["umin2_soft_50_1"] = soft_run(q, 50.0, 1.0)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config4", action="store_true")
+    ap.add_argument("--soft", action="store_true")
+    ap.add_argument("--ab-lib", default=None)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--horizon", type=int, default=None, help="--soft: N of the session-2 problem")
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=3)
@@ -86,6 +212,14 @@ def main():
     a = ap.parse_args()
     assert a.repeats >= 10
     dev = torch.device("cuda:0")
+    if a.soft:
+        line = json.dumps(soft_mode(a, dev))
+        print(line)
+        if a.json:
+            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+            with open(a.json, "a") as f:
+                f.write(line + "\n")
+        return
     p = (_config4 if a.config4 else _session2)(a.batch, dev)
     qp, A, B, x0, hl, hu, E = (p[k] for k in ("qp", "A", "B", "x0", "hl", "hu", "E"))
     b, T, nx, nu, n = a.batch, a.steps, A.shape[0], B.shape[1], qp.n
