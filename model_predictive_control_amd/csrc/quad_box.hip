@@ -216,6 +216,9 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
 #ifdef MPCQP_PHASE_TIMING
   PhaseClock mpcqp_clk;
 #endif
+  // Without a drift (wave-uniform) Cs is neither filled nor read: the x-bar
+  // sums start from 0, which is what they would read.
+  const bool has_c = a.c != nullptr;
   // ------------------------------------------------------------- stage in
   bool nonfinite = false, badbox = false;
   {
@@ -269,7 +272,7 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
       Qfs[q] = vQf;
     }
     if (q < NU * NU) Rs[q] = vR;
-    if (q < N * NX) Cs[q] = vC;
+    if (q < N * NX && has_c) Cs[q] = vC;
     if (q < NX) X0s[q] = vX0;
 #pragma unroll
     for (int t = 0; t < NB; ++t) {
@@ -295,8 +298,10 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
       Bs[e] = v;
       nonfinite |= !finite(v);
     }
+    if (has_c) {
 #pragma unroll 4
-    for (int e = q + GL; e < N * NX; e += GL) Cs[e] = ldC(e);
+      for (int e = q + GL; e < N * NX; e += GL) Cs[e] = ldC(e);
+    }
   }
   __syncthreads();
 
@@ -318,13 +323,37 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
 #pragma unroll
     for (int qq = 0; qq < NX; ++qq) xk[qq] = X0s[qq];
     bool ok = true;
+    // c_t: not read without a drift.  With one it is read a stage ahead, so
+    // that the wait in front of its use does not also wait for the K, S^-1 and
+    // A + BK stores of the stage before (NX <= 2; the NX = 4 loop has no
+    // registers to spare and reads it at its use).
+    constexpr bool C_AHEAD = NX <= 2;
+    [[maybe_unused]] T ct[NX];
+    if constexpr (C_AHEAD) {
+#pragma unroll
+      for (int i = 0; i < NX; ++i) ct[i] = has_c ? Cs[i] : T(0);
+    }
     for (int t = 0; t < N; ++t) {
       {  // x-bar stage t: x_{t+1} = A_t x_t + c_t
         if (tv) load_sq<T, NX, NX>(As + t * NX * NX, Ax, NX);
-        T xn[NX];
+        T xn[NX], cs[NX];
+#pragma unroll
+        for (int i = 0; i < NX; ++i) cs[i] = T(0);
+        if constexpr (C_AHEAD) {
+#pragma unroll
+          for (int i = 0; i < NX; ++i) cs[i] = ct[i];
+          if (has_c) {
+            const int tn = t + 1 < N ? t + 1 : t;
+#pragma unroll
+            for (int i = 0; i < NX; ++i) ct[i] = Cs[tn * NX + i];
+          }
+        } else if (has_c) {
+#pragma unroll
+          for (int i = 0; i < NX; ++i) cs[i] = Cs[t * NX + i];
+        }
 #pragma unroll
         for (int i = 0; i < NX; ++i) {
-          T s = Cs[t * NX + i];
+          T s = cs[i];
 #pragma unroll
           for (int qq = 0; qq < NX; ++qq) s = fma(Ax[i][qq], xk[qq], s);
           xn[i] = s;

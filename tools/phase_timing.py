@@ -11,7 +11,7 @@ CS = os.environ.get("PT_CS", os.path.join(ROOT, "model_predictive_control_amd", 
 LIB = os.path.join(ROOT, "model_predictive_control_amd", "lib", "libmpcqp_timing.so")
 SRCS = ["api.cpp", "condense.hip", "solve_box.hip", "solve_poly.hip", "mpc_box.hip", "quad_box.hip",
         "solve_qp.hip", "sweep.hip", "solve_pf.hip", "solve_zf.hip", "fallback64.hip", "mpc_qp.hip", "bicycle.hip", "misc.hip",
-        "ipm.hip", "sqp.hip", "sqp_solve.hip", "loop_box.hip"]
+        "ipm.hip", "sqp.hip", "sqp_solve.hip", "loop_box.hip", "loop_poly.hip"]
 PHASES = ["stage-in", "Riccati + xbar", "W~ columns + adjoint", "M = -W~W~' product", "GI: refresh/recheck", "GI: scan+argmax", "GI: pivot col+ratio", "GI: sweep"]
 
 DYN = "--dyn" in sys.argv or (len(sys.argv) > 1 and sys.argv[1].startswith("dyn"))
