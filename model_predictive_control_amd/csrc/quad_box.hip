@@ -13,11 +13,25 @@
 // unit lower block triangular, so H^{-1} = W diag(S_k^{-1}) W' with W = T^{-1}
 // (mpc_factor.hpp).  In order:
 //   1. stage in: every global load of the group is issued before the first wait;
-//   2. Riccati stage N-1-t next to free-response (x-bar) stage t, one loop;
-//   3. every lane rolls its column(s) of W~ = W diag(chol(S_k^{-1})) forward in
-//      lockstep over the stages (closed loop from u_j = L_j[:, b]; K_k and
-//      A_k + B_k K_k are broadcast LDS reads), next to the backward adjoint
-//      y_k = Q xbar_k + A_k'y_{k+1} that yields f_k = B_k'y_{k+1};
+//   2. Riccati stage N-1-t next to free-response (x-bar) stage t, one loop.
+//      Row form (QMpcRows; nx <= 2): the same loop generates
+//      W~ = W diag(chol(S_k^{-1})) by rows, backward in the column stage: at
+//      Riccati step j, K_j, A_j + B_j K_j, B_j and S_j^-1 are in the registers
+//      of every lane, and lane q, which owns rows q and q + 16, writes its
+//      entries of the nu columns of stage j from one 1 x NX row vector per
+//      row (mpc_factor.hpp) -- no LDS read at all.  f comes from the
+//      x0-independent backward form of the adjoint, y_k = Pi_k xbar_k + pi_k:
+//          Pi_k = Q + A_k' Pi_{k+1} A_k,  pi_k = A_k'(Pi_{k+1} c_k + pi_{k+1}),
+//          f_k = (B_k' Pi_{k+1}) xbar_{k+1} + B_k' pi_{k+1},   Pi_N = Qf, pi_N = 0
+//      (pi only with a drift), whose recursion also runs in this loop; the
+//      row's lane catches g_k = B_k' Pi_{k+1} at backward step k and
+//      xbar_{k+1} at forward step k, and f is one short dot product per row
+//      after the loop;
+//   3. two-loop form (the other instantiations): every lane rolls its
+//      column(s) of W~ forward in lockstep over the stages in a second loop
+//      (closed loop from u_j = L_j[:, b]; K_k and A_k + B_k K_k are broadcast
+//      LDS reads), next to the backward adjoint y_k = Q xbar_k + A_k'y_{k+1}
+//      that yields f_k = B_k'y_{k+1};
 //   4. M = -W~ W~' accumulated from the LDS tile straight into the register
 //      blocks, bitwise symmetric;
 //   5. Goldfarb-Idnani on M (quad.hpp).
@@ -121,16 +135,42 @@ __global__ __launch_bounds__(64, (QuadOcc<T, BS>::w)) void box_quad_kernel(BoxAr
 }
 
 // ----------------------------------------------------------- fused kernel
+// Which instantiations of mpc_group_kernel generate W~ by rows inside the
+// Riccati loop (true) and which keep the two-loop setup, W~ by columns in a
+// second loop (false).  The row form carries, next to the Riccati state, one
+// NX-vector per owned row for each of Psi, g and x-bar plus the NX x NX
+// Lyapunov matrix Pi.  Registers, scratch bytes per lane and occupancy bound
+// of the built kernels (two-loop -> rows):
+//   fp64 NX = 4:                 scratch 0..52 -> 364..528 bytes (BS <= 5)
+//   fp32 NX = 4:                 124..167 -> 168..228 VGPRs, bound 3..4 -> 2..3 waves
+//   fp64 NX = 2, NU = 2, BS <= 3: scratch 0..24 -> 72 bytes under the 128 VGPRs
+//                                 of their four-wave bound, and measured 3-6 %
+//                                 slower (B = 4096: n = 4 13.1 -> 13.6 us, n = 8
+//                                 time-varying 18.0 -> 19.0, n = 12 30.4 -> 31.5)
+// Those stay on two loops.  Every other one takes the row form: the config-2
+// instantiation (fp64 NX = 2 NU = 1 BS = 5) has 209 VGPRs and no scratch both
+// ways, none gains scratch, and only fp64 NX = 2 NU = 1 BS = 1 loses a wave of
+// its occupancy bound (86 -> 115 VGPRs, 5 -> 4) while measuring faster (n = 1
+// 6.1 -> 5.7 us, n = 4 11.4 -> 10.7).
+template <typename T, int NX, int NU, int BS>
+struct QMpcRows {
+  static constexpr bool v = NX <= 2 && !(sizeof(T) == 8 && NU == 2 && BS <= 3);
+};
+
 template <typename T, int NX, int NU, class Mat>
 struct QMpcLds {
-  // oW: the W~ tile, column c at oW + c*ld, all Mat::NV rows written.  ld is
-  // odd, so the 16 lanes of a group, each storing one row of its own column
-  // (8-byte stores, 16 consecutive lanes per LDS cycle, 32 four-byte banks),
-  // hit 16 distinct bank pairs; the Gram product reads a lane's BS rows of one
-  // column contiguously (mpc_factor.hpp).
+  static constexpr bool ROWS = QMpcRows<T, NX, NU, Mat::RPL>::v;
+  // oW: the W~ tile, column c at oW + c*ld, all Mat::NV rows written.  Row
+  // form: the 16 lanes of a group store consecutive rows of one column.
+  // Column form: each lane stores one row of its own column; ld is odd, so
+  // the 16 lanes (8-byte stores, 32 four-byte banks) hit 16 distinct bank
+  // pairs.  The Gram product reads a lane's BS rows of one column
+  // contiguously (mpc_factor.hpp).  oK, oSi, oAcl, oX: K_k, S_k^-1, A_k + B_k K_k
+  // and x-bar for the second loop of the two-loop setup (empty in row form).
   int oA, oB, oQ, oQf, oR, oC, oX0, oK, oSi, oAcl, oX, oW, total, ld;
   __host__ __device__ QMpcLds(int N, int n, int tv) {
     const int S = tv ? N : 1;
+    const int N2 = ROWS ? 0 : N;
     oA = GBoxLds<Mat>::size;
     oB = oA + S * NX * NX;
     oQ = oB + S * NX * NU;
@@ -139,10 +179,10 @@ struct QMpcLds {
     oC = oR + NU * NU;
     oX0 = oC + N * NX;
     oK = oX0 + NX;
-    oSi = oK + N * NU * NX;
-    oAcl = oSi + N * NU * NU;
-    oX = oAcl + N * NX * NX;
-    oW = oX + (N + 1) * NX;
+    oSi = oK + N2 * NU * NX;
+    oAcl = oSi + N2 * NU * NU;
+    oX = oAcl + N2 * NX * NX;
+    oW = oX + (ROWS ? 0 : (N + 1) * NX);
     ld = Mat::NV + 1;
     total = (oW + n * ld + 1) & ~1;  // keep every group's base 16-byte aligned
   }
@@ -206,10 +246,11 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
   T* Rs = sm + L.oR;
   T* Cs = sm + L.oC;
   T* X0s = sm + L.oX0;
-  T* Ks = sm + L.oK;
-  T* Sis = sm + L.oSi;
-  T* Acls = sm + L.oAcl;
-  T* Xs = sm + L.oX;
+  constexpr bool ROWS = QMpcRows<T, NX, NU, RPL>::v;
+  [[maybe_unused]] T* Ks = sm + L.oK;
+  [[maybe_unused]] T* Sis = sm + L.oSi;
+  [[maybe_unused]] T* Acls = sm + L.oAcl;
+  [[maybe_unused]] T* Xs = sm + L.oX;
   T* Wt = sm + L.oW;
   const int ld = L.ld;
 
@@ -312,6 +353,7 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
   // stage N-1-t next to x-bar stage t so that their latencies overlap (at one
   // wave per SIMD nothing else hides them).
   {
+    constexpr int NCH = (NV + GL - 1) / GL;  // rows (row form) / columns of W~ per lane
     T P[NX][NX], Qr[NX][NX], Rr[NU][NU], Ar[NX][NX], Br[NX][NU], Ax[NX][NX];
     load_sq<T, NX, NX>(Qfs, P, NX);
     load_sq<T, NX, NX>(Qs, Qr, NX);
@@ -323,9 +365,33 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
 #pragma unroll
     for (int qq = 0; qq < NX; ++qq) xk[qq] = X0s[qq];
     bool ok = true;
-    // c_t: not read without a drift.  With one it is read a stage ahead, so
-    // that the wait in front of its use does not also wait for the K, S^-1 and
-    // A + BK stores of the stage before (NX <= 2; the NX = 4 loop has no
+    // Rows of W~ and of f: lane q owns rows r = q + ch*GL < NV, row r being
+    // input a = r % nu of stage rt = r / nu (rt = -1 for the padding rows
+    // n .. NV-1, which no stage matches: their chain stays 0).  psi is the
+    // row vector Psi_j(rt)[a, :], gr / hr / xr the row's g_rt[a, :], h_rt[a]
+    // and xbar_{rt+1}, each caught at the step that holds it in registers.
+    // Pi, pv: y_k = Pi_k xbar_k + pi_k (pi only with a drift).
+    [[maybe_unused]] int rt[NCH];
+    [[maybe_unused]] bool ra1[NCH];
+    [[maybe_unused]] T psi[NCH][NX], gr[NCH][NX], xr[NCH][NX], hr[NCH], Pi[NX][NX], pv[NX];
+    if constexpr (ROWS) {
+#pragma unroll
+      for (int ch = 0; ch < NCH; ++ch) {
+        const int r = q + ch * GL;
+        const int tr = r / nu;
+        rt[ch] = r < n ? tr : -1;
+        ra1[ch] = r - tr * nu == 1;
+        hr[ch] = T(0);
+#pragma unroll
+        for (int qq = 0; qq < NX; ++qq) psi[ch][qq] = gr[ch][qq] = xr[ch][qq] = T(0);
+      }
+      load_sq<T, NX, NX>(Qfs, Pi, NX);
+#pragma unroll
+      for (int qq = 0; qq < NX; ++qq) pv[qq] = T(0);
+    }
+    // c_t: not read without a drift.  With one, the x-bar stage reads it a
+    // stage ahead, so that the wait in front of its use does not also wait
+    // for the LDS stores of the stage before (NX <= 2; the NX = 4 loop has no
     // registers to spare and reads it at its use).
     constexpr bool C_AHEAD = NX <= 2;
     [[maybe_unused]] T ct[NX];
@@ -360,9 +426,15 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
         }
 #pragma unroll
         for (int qq = 0; qq < NX; ++qq) xk[qq] = xn[qq];
-        if (q == 0)
+        if constexpr (ROWS) {
+#pragma unroll
+          for (int ch = 0; ch < NCH; ++ch)
+#pragma unroll
+            for (int qq = 0; qq < NX; ++qq) xr[ch][qq] = t == rt[ch] ? xk[qq] : xr[ch][qq];
+        } else if (q == 0) {
 #pragma unroll
           for (int qq = 0; qq < NX; ++qq) Xs[(t + 1) * NX + qq] = xk[qq];
+        }
       }
       const int k = N - 1 - t;
       if (tv) {
@@ -407,6 +479,7 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
       }
       // S^{-1} by Gauss-Jordan (S symmetric positive definite)
       T Si[NU][NU];
+      [[maybe_unused]] const T s00 = Sm[0][0];
 #pragma unroll
       for (int i = 0; i < NU; ++i)
 #pragma unroll
@@ -441,14 +514,30 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
           for (int qq = 0; qq < NU; ++qq) s = fma(Si[i][qq], Y[qq][j], s);
           K[i][j] = -s;
         }
-      if (q == 0) {
+      if constexpr (!ROWS) {
+        // two-loop setup: K_k, S_k^-1 and A_k + B_k K_k for the second loop
+        if (q == 0) {
 #pragma unroll
-        for (int i = 0; i < NU; ++i) {
+          for (int i = 0; i < NU; ++i) {
 #pragma unroll
-          for (int j = 0; j < NX; ++j) Ks[(k * NU + i) * NX + j] = K[i][j];
+            for (int j = 0; j < NX; ++j) Ks[(k * NU + i) * NX + j] = K[i][j];
 #pragma unroll
-          for (int j = 0; j < NU; ++j) Sis[(k * NU + i) * NU + j] = Si[i][j];
+            for (int j = 0; j < NU; ++j) Sis[(k * NU + i) * NU + j] = Si[i][j];
+          }
+#pragma unroll
+          for (int i = 0; i < NX; ++i)
+#pragma unroll
+            for (int j = 0; j < NX; ++j) {
+              T s = Ar[i][j];
+#pragma unroll
+              for (int qq = 0; qq < NU; ++qq) s = fma(Br[i][qq], K[qq][j], s);
+              Acls[(k * NX + i) * NX + j] = s;
+            }
         }
+      } else {
+        // row form: columns (k, :) of W~, the rows of every lane; then
+        // Psi_{k-1} (mpc_factor.hpp)
+        T Acl[NX][NX], Lk[NU][NU];
 #pragma unroll
         for (int i = 0; i < NX; ++i)
 #pragma unroll
@@ -456,10 +545,119 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
             T s = Ar[i][j];
 #pragma unroll
             for (int qq = 0; qq < NU; ++qq) s = fma(Br[i][qq], K[qq][j], s);
-            Acls[(k * NX + i) * NX + j] = s;
+            Acl[i][j] = s;
           }
+        chol_lower<T, NU>(s00, Si, Lk);
+#pragma unroll
+        for (int ch = 0; ch < NCH; ++ch) {
+          const bool at = k == rt[ch];
+          // v = e_a' at the row's own stage, Psi_k(rt)[a, :] B_k after it.  The
+          // rows of earlier stages (rt < k) and the padding rows n .. NV-1
+          // store 0 * B_k * L_k, which is 0 only while those are finite: in
+          // the NOT_CONVEX case (NaN or Inf in L_k, K_k) the tile holds NaN
+          // there, which nothing uses -- gi_box runs only with code ==
+          // OPTIMAL and z is overwritten with NaN.
+          T v[NU], w[NU];
+#pragma unroll
+          for (int i = 0; i < NU; ++i) {
+            T s = T(0);
+#pragma unroll
+            for (int qq = 0; qq < NX; ++qq) s = fma(psi[ch][qq], Br[qq][i], s);
+            v[i] = at ? (ra1[ch] == (i == 1) ? T(1) : T(0)) : s;
+          }
+          // w = v L_k (L_k lower triangular)
+#pragma unroll
+          for (int bb = 0; bb < NU; ++bb) {
+            T s = v[bb] * Lk[bb][bb];
+#pragma unroll
+            for (int i = bb + 1; i < NU; ++i) s = fma(v[i], Lk[i][bb], s);
+            w[bb] = s;
+          }
+          if (q + ch * GL < NV) {
+#pragma unroll
+            for (int bb = 0; bb < NU; ++bb)
+              if (bb < nu) Wt[(k * nu + bb) * ld + q + ch * GL] = w[bb];
+          }
+          T pn[NX];
+#pragma unroll
+          for (int j = 0; j < NX; ++j) {
+            T s = T(0);
+#pragma unroll
+            for (int qq = 0; qq < NX; ++qq) s = fma(psi[ch][qq], Acl[qq][j], s);
+            pn[j] = at ? (ra1[ch] ? K[NU - 1][j] : K[0][j]) : s;
+          }
+#pragma unroll
+          for (int j = 0; j < NX; ++j) psi[ch][j] = pn[j];
+        }
+        // g_k = B_k' Pi_{k+1}, h_k = B_k' pi_{k+1}, caught by the rows of stage
+        // k; then Pi_k = Q + A_k' Pi_{k+1} A_k, pi_k = A_k'(Pi_{k+1} c_k + pi_{k+1})
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+          T gu[NX];
+#pragma unroll
+          for (int j = 0; j < NX; ++j) {
+            T s = T(0);
+#pragma unroll
+            for (int qq = 0; qq < NX; ++qq) s = fma(Br[qq][u], Pi[qq][j], s);
+            gu[j] = s;
+          }
+#pragma unroll
+          for (int ch = 0; ch < NCH; ++ch) {
+            const bool mine = k == rt[ch] && ra1[ch] == (u == 1);
+#pragma unroll
+            for (int j = 0; j < NX; ++j) gr[ch][j] = mine ? gu[j] : gr[ch][j];
+          }
+          if (has_c) {
+            T hu = T(0);
+#pragma unroll
+            for (int qq = 0; qq < NX; ++qq) hu = fma(Br[qq][u], pv[qq], hu);
+#pragma unroll
+            for (int ch = 0; ch < NCH; ++ch)
+              hr[ch] = (k == rt[ch] && ra1[ch] == (u == 1)) ? hu : hr[ch];
+          }
+        }
+        // (also at k = 0, where the results are not used: without the branch
+        // the loop carries no copies of Pi and P)
+        {
+          if (has_c) {
+            T tmp[NX];
+#pragma unroll
+            for (int i = 0; i < NX; ++i) {
+              T s = pv[i];
+#pragma unroll
+              for (int qq = 0; qq < NX; ++qq) s = fma(Pi[i][qq], Cs[k * NX + qq], s);
+              tmp[i] = s;
+            }
+#pragma unroll
+            for (int i = 0; i < NX; ++i) {
+              T s = T(0);
+#pragma unroll
+              for (int qq = 0; qq < NX; ++qq) s = fma(Ar[qq][i], tmp[qq], s);
+              pv[i] = s;
+            }
+          }
+          T PiA[NX][NX];
+#pragma unroll
+          for (int i = 0; i < NX; ++i)
+#pragma unroll
+            for (int j = 0; j < NX; ++j) {
+              T s = T(0);
+#pragma unroll
+              for (int qq = 0; qq < NX; ++qq) s = fma(Pi[i][qq], Ar[qq][j], s);
+              PiA[i][j] = s;
+            }
+#pragma unroll
+          for (int i = 0; i < NX; ++i)
+#pragma unroll
+            for (int j = 0; j < NX; ++j) {
+              T s = Qr[i][j];
+#pragma unroll
+              for (int qq = 0; qq < NX; ++qq) s = fma(Ar[qq][i], PiA[qq][j], s);
+              Pi[i][j] = s;
+            }
+        }
       }
-      if (k > 0) {
+      if (ROWS || k > 0) {
         // P <- Q + A'PA + (A'PB) K
 #pragma unroll
         for (int i = 0; i < NX; ++i)
@@ -482,143 +680,154 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
     if (!ok) code = MPCQP_STATUS_NOT_CONVEX;
 
     MPCQP_PHASE(1);
-    // ---- columns of W~ (forward, lockstep) next to the adjoint y -> f
-    // (backward).  Lane q rolls column c = q (and c = q + GL when n > GL) of
-    // W~ (mpc_factor.hpp): with v_t = L_j[:, b] at the column's own stage
-    // t = j and 0 elsewhere,
-    //     u_t = K_t x_t + v_t,   x_{t+1} = (A_t + B_t K_t) x_t + B_t v_t,
-    // which is 0 before stage j, the start at j and the closed loop after it.
-    // Every lane is at the same stage, so Ks, Acls and Bs are broadcast reads.
-    // The adjoint is group-uniform and independent of the rollouts: stage
-    // N-1-t runs next to rollout stage t so that the two chains overlap; its
-    // x_k of the next stage is read from LDS one iteration ahead.
-    __syncthreads();
-    constexpr int NCH = (NV + GL - 1) / GL;  // columns per lane
-    bool cv[NCH];
-    int cj[NCH];
-    T lj[NCH][NU], wx[NCH][NX];
-    T* Wc[NCH];
+    if constexpr (ROWS) {
+      // f_(t,a) = g_t[a, :] xbar_{t+1} + h_t[a] for the lane's own rows (the rows
+      // n .. NV-1 keep the 0 of the stage-in)
 #pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) {
-      const int c = q + ch * GL;
-      cv[ch] = c < n;
-      const int cc = cv[ch] ? c : 0;
-      const int jj = cc / nu;
-      cj[ch] = cv[ch] ? jj : -1;
-      chol_col<T, NU>(Sis + jj * NU * NU, cc - jj * nu, lj[ch]);
-      Wc[ch] = Wt + cc * ld;
+      for (int ch = 0; ch < NCH; ++ch) {
+        T s = hr[ch];
 #pragma unroll
-      for (int qq = 0; qq < NX; ++qq) wx[ch][qq] = T(0);
-    }
-    T yk[NX];
-#pragma unroll
-    for (int i = 0; i < NX; ++i) {
-      T s = T(0);
-#pragma unroll
-      for (int qq = 0; qq < NX; ++qq) s = fma(Qfs[i * NX + qq], xk[qq], s);
-      yk[i] = s;
-    }
-    T xnext[NX];
-#pragma unroll
-    for (int qq = 0; qq < NX; ++qq) xnext[qq] = Xs[(N - 1) * NX + qq];
-    // B of the rollout stage (Br) and of the adjoint stage (Ba) and A of the
-    // adjoint stage (Ar) stay in registers for the whole loop unless the
-    // plant is time-varying.  Every LDS read of an iteration is issued at its
-    // top, before its stores (which the compiler must assume alias them);
-    // K, A + B K and x-bar are read one stage ahead, after the time-varying
-    // reads so that a counted wait for those leaves them in flight.  With an
-    // invariant plant no stage waits for a read it has just issued.
-    T Ba[NX][NU], Kt[NU][NX], Act[NX][NX];
-    load_sq<T, NX, NU>(Bs, Br, NU);
-    load_sq<T, NX, NU>(Bs, Ba, NU);
-    load_sq<T, NU, NX>(Ks, Kt, NX);
-    load_sq<T, NX, NX>(Acls, Act, NX);
-    for (int t = 0; t < N; ++t) {
-      const int k = N - 1 - t;  // adjoint stage
-      if (tv) {
-        load_sq<T, NX, NU>(Bs + t * NX * NU, Br, NU);
-        load_sq<T, NX, NU>(Bs + k * NX * NU, Ba, NU);
-        load_sq<T, NX, NX>(As + k * NX * NX, Ar, NX);
+        for (int qq = 0; qq < NX; ++qq) s = fma(gr[ch][qq], xr[ch][qq], s);
+        if (rt[ch] >= 0) fs[q + ch * GL] = s;
       }
-      const int tn = t + 1 < N ? t + 1 : t;
-      T Kn[NU][NX], Acn[NX][NX], xnn[NX];
-      load_sq<T, NU, NX>(Ks + tn * NU * NX, Kn, NX);
-      load_sq<T, NX, NX>(Acls + tn * NX * NX, Acn, NX);
+    } else {
+      // ---- columns of W~ (forward, lockstep) next to the adjoint y -> f
+      // (backward).  Lane q rolls column c = q (and c = q + GL when n > GL) of
+      // W~ (mpc_factor.hpp): with v_t = L_j[:, b] at the column's own stage
+      // t = j and 0 elsewhere,
+      //     u_t = K_t x_t + v_t,   x_{t+1} = (A_t + B_t K_t) x_t + B_t v_t,
+      // which is 0 before stage j, the start at j and the closed loop after it.
+      // Every lane is at the same stage, so Ks, Acls and Bs are broadcast reads.
+      // The adjoint is group-uniform and independent of the rollouts: stage
+      // N-1-t runs next to rollout stage t so that the two chains overlap; its
+      // x_k of the next stage is read from LDS one iteration ahead.
+      __syncthreads();
+      bool cv[NCH];  // NCH: columns per lane here
+      int cj[NCH];
+      T lj[NCH][NU], wx[NCH][NX];
+      T* Wc[NCH];
 #pragma unroll
-      for (int qq = 0; qq < NX; ++qq) xnn[qq] = Xs[(k > 1 ? k - 1 : 1) * NX + qq];
-      {  // rollout stage t
+      for (int ch = 0; ch < NCH; ++ch) {
+        const int c = q + ch * GL;
+        cv[ch] = c < n;
+        const int cc = cv[ch] ? c : 0;
+        const int jj = cc / nu;
+        cj[ch] = cv[ch] ? jj : -1;
+        chol_col<T, NU>(Sis + jj * NU * NU, cc - jj * nu, lj[ch]);
+        Wc[ch] = Wt + cc * ld;
 #pragma unroll
-        for (int ch = 0; ch < NCH; ++ch) {
-          const bool at = t == cj[ch];
-          T v[NU], u[NU], xn[NX];
+        for (int qq = 0; qq < NX; ++qq) wx[ch][qq] = T(0);
+      }
+      T yk[NX];
 #pragma unroll
-          for (int i = 0; i < NU; ++i) {
-            v[i] = at ? lj[ch][i] : T(0);
-            T s = v[i];
+      for (int i = 0; i < NX; ++i) {
+        T s = T(0);
 #pragma unroll
-            for (int qq = 0; qq < NX; ++qq) s = fma(Kt[i][qq], wx[ch][qq], s);
-            u[i] = s;
+        for (int qq = 0; qq < NX; ++qq) s = fma(Qfs[i * NX + qq], xk[qq], s);
+        yk[i] = s;
+      }
+      T xnext[NX];
+#pragma unroll
+      for (int qq = 0; qq < NX; ++qq) xnext[qq] = Xs[(N - 1) * NX + qq];
+      // B of the rollout stage (Br) and of the adjoint stage (Ba) and A of the
+      // adjoint stage (Ar) stay in registers for the whole loop unless the
+      // plant is time-varying.  Every LDS read of an iteration is issued at its
+      // top, before its stores (which the compiler must assume alias them);
+      // K, A + B K and x-bar are read one stage ahead, after the time-varying
+      // reads so that a counted wait for those leaves them in flight.  With an
+      // invariant plant no stage waits for a read it has just issued.
+      T Ba[NX][NU], Kt[NU][NX], Act[NX][NX];
+      load_sq<T, NX, NU>(Bs, Br, NU);
+      load_sq<T, NX, NU>(Bs, Ba, NU);
+      load_sq<T, NU, NX>(Ks, Kt, NX);
+      load_sq<T, NX, NX>(Acls, Act, NX);
+      for (int t = 0; t < N; ++t) {
+        const int k = N - 1 - t;  // adjoint stage
+        if (tv) {
+          load_sq<T, NX, NU>(Bs + t * NX * NU, Br, NU);
+          load_sq<T, NX, NU>(Bs + k * NX * NU, Ba, NU);
+          load_sq<T, NX, NX>(As + k * NX * NX, Ar, NX);
+        }
+        const int tn = t + 1 < N ? t + 1 : t;
+        T Kn[NU][NX], Acn[NX][NX], xnn[NX];
+        load_sq<T, NU, NX>(Ks + tn * NU * NX, Kn, NX);
+        load_sq<T, NX, NX>(Acls + tn * NX * NX, Acn, NX);
+#pragma unroll
+        for (int qq = 0; qq < NX; ++qq) xnn[qq] = Xs[(k > 1 ? k - 1 : 1) * NX + qq];
+        {  // rollout stage t
+#pragma unroll
+          for (int ch = 0; ch < NCH; ++ch) {
+            const bool at = t == cj[ch];
+            T v[NU], u[NU], xn[NX];
+#pragma unroll
+            for (int i = 0; i < NU; ++i) {
+              v[i] = at ? lj[ch][i] : T(0);
+              T s = v[i];
+#pragma unroll
+              for (int qq = 0; qq < NX; ++qq) s = fma(Kt[i][qq], wx[ch][qq], s);
+              u[i] = s;
+            }
+#pragma unroll
+            for (int i = 0; i < NX; ++i) {
+              T s = T(0);
+#pragma unroll
+              for (int qq = 0; qq < NX; ++qq) s = fma(Act[i][qq], wx[ch][qq], s);
+#pragma unroll
+              for (int qq = 0; qq < NU; ++qq) s = fma(Br[i][qq], v[qq], s);
+              xn[i] = s;
+            }
+#pragma unroll
+            for (int qq = 0; qq < NX; ++qq) wx[ch][qq] = xn[qq];
+            // every row is written, the zeros before stage j included
+            if (cv[ch]) {
+#pragma unroll
+              for (int i = 0; i < NU; ++i)
+                if (i < nu) Wc[ch][t * nu + i] = u[i];
+            }
           }
+        }
+        // adjoint stage k: f_(k,u) = B_k[:,u]' y_{k+1}, then y_k
+        if (q == 0) {
+#pragma unroll
+          for (int u = 0; u < NU; ++u) {
+            T s = T(0);
+#pragma unroll
+            for (int qq = 0; qq < NX; ++qq) s = fma(Ba[qq][u], yk[qq], s);
+            if (u < nu) fs[k * nu + u] = s;
+          }
+        }
+        if (k > 0) {
+          T yn[NX];
 #pragma unroll
           for (int i = 0; i < NX; ++i) {
             T s = T(0);
 #pragma unroll
-            for (int qq = 0; qq < NX; ++qq) s = fma(Act[i][qq], wx[ch][qq], s);
+            for (int qq = 0; qq < NX; ++qq) s = fma(Qr[i][qq], xnext[qq], s);
 #pragma unroll
-            for (int qq = 0; qq < NU; ++qq) s = fma(Br[i][qq], v[qq], s);
-            xn[i] = s;
+            for (int qq = 0; qq < NX; ++qq) s = fma(Ar[qq][i], yk[qq], s);
+            yn[i] = s;
           }
 #pragma unroll
-          for (int qq = 0; qq < NX; ++qq) wx[ch][qq] = xn[qq];
-          // every row is written, the zeros before stage j included
-          if (cv[ch]) {
-#pragma unroll
-            for (int i = 0; i < NU; ++i)
-              if (i < nu) Wc[ch][t * nu + i] = u[i];
-          }
+          for (int qq = 0; qq < NX; ++qq) yk[qq] = yn[qq];
         }
+        // next stage's operands
+#pragma unroll
+        for (int i = 0; i < NU; ++i)
+#pragma unroll
+          for (int qq = 0; qq < NX; ++qq) Kt[i][qq] = Kn[i][qq];
+#pragma unroll
+        for (int i = 0; i < NX; ++i)
+#pragma unroll
+          for (int qq = 0; qq < NX; ++qq) Act[i][qq] = Acn[i][qq];
+#pragma unroll
+        for (int qq = 0; qq < NX; ++qq) xnext[qq] = xnn[qq];
       }
-      // adjoint stage k: f_(k,u) = B_k[:,u]' y_{k+1}, then y_k
-      if (q == 0) {
+      // rows n .. NV-1 of the lane's columns: the padding of the register layout
 #pragma unroll
-        for (int u = 0; u < NU; ++u) {
-          T s = T(0);
-#pragma unroll
-          for (int qq = 0; qq < NX; ++qq) s = fma(Ba[qq][u], yk[qq], s);
-          if (u < nu) fs[k * nu + u] = s;
-        }
-      }
-      if (k > 0) {
-        T yn[NX];
-#pragma unroll
-        for (int i = 0; i < NX; ++i) {
-          T s = T(0);
-#pragma unroll
-          for (int qq = 0; qq < NX; ++qq) s = fma(Qr[i][qq], xnext[qq], s);
-#pragma unroll
-          for (int qq = 0; qq < NX; ++qq) s = fma(Ar[qq][i], yk[qq], s);
-          yn[i] = s;
-        }
-#pragma unroll
-        for (int qq = 0; qq < NX; ++qq) yk[qq] = yn[qq];
-      }
-      // next stage's operands
-#pragma unroll
-      for (int i = 0; i < NU; ++i)
-#pragma unroll
-        for (int qq = 0; qq < NX; ++qq) Kt[i][qq] = Kn[i][qq];
-#pragma unroll
-      for (int i = 0; i < NX; ++i)
-#pragma unroll
-        for (int qq = 0; qq < NX; ++qq) Act[i][qq] = Acn[i][qq];
-#pragma unroll
-      for (int qq = 0; qq < NX; ++qq) xnext[qq] = xnn[qq];
+      for (int ch = 0; ch < NCH; ++ch)
+        if (cv[ch])
+          for (int i = n; i < NV; ++i) Wc[ch][i] = T(0);
     }
-    // rows n .. NV-1 of the lane's columns: the padding of the register layout
-#pragma unroll
-    for (int ch = 0; ch < NCH; ++ch)
-      if (cv[ch])
-        for (int i = n; i < NV; ++i) Wc[ch][i] = T(0);
   }
   __syncthreads();
 

@@ -12,7 +12,10 @@ LIB = os.path.join(ROOT, "model_predictive_control_amd", "lib", "libmpcqp_timing
 SRCS = ["api.cpp", "condense.hip", "solve_box.hip", "solve_poly.hip", "mpc_box.hip", "quad_box.hip",
         "solve_qp.hip", "sweep.hip", "solve_pf.hip", "solve_zf.hip", "fallback64.hip", "mpc_qp.hip", "bicycle.hip", "misc.hip",
         "ipm.hip", "sqp.hip", "sqp_solve.hip", "loop_box.hip", "loop_poly.hip"]
-PHASES = ["stage-in", "Riccati + xbar", "W~ columns + adjoint", "M = -W~W~' product", "GI: refresh/recheck", "GI: scan+argmax", "GI: pivot col+ratio", "GI: sweep"]
+# (config 2 is on the row form: phase 1 holds the W~ rows and the Pi recursion
+# as well, phase 2 only the f dot products and the barrier; the two-loop
+# instantiations spend phase 2 on the W~ columns and the adjoint)
+PHASES = ["stage-in", "Riccati + xbar + W~ rows", "f rows (two-loop: W~ columns + adjoint)", "M = -W~W~' product", "GI: refresh/recheck", "GI: scan+argmax", "GI: pivot col+ratio", "GI: sweep"]
 
 DYN = "--dyn" in sys.argv or (len(sys.argv) > 1 and sys.argv[1].startswith("dyn"))
 if DYN:  # a separate library whose pf kernel clock times the DYN refinement
