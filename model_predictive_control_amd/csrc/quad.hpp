@@ -115,8 +115,26 @@ struct QSym {
       }
   }
 
+  // Row ownership (RowOwn below): row r of a row block belongs to lane
+  // bj = r mod 4, so a lane owns RO rows, slot s holding row 4 s + bj.
+  static constexpr int RO = (BS + 3) / 4;
+  __device__ __forceinline__ int own_row(int s) const { return 4 * s + bj; }
+  __device__ __forceinline__ bool owns(int s) const { return own_row(s) < BS; }
+  // the same for addressing: a slot without a row reads the block's last row
+  __device__ __forceinline__ int own_mrow(int s) const {
+    return own_row(s) < BS ? own_row(s) : BS - 1;
+  }
+
   // Column k (group-uniform) through the group's LDS tile; returns M_kk.
+  // (the owners' reads below are dead here: their results are never used,
+  // and the compiler drops the loads -- same ds_read count as before)
   __device__ __forceinline__ T column(int k, T* gb, T (&colr)[BS], T (&colc)[BS]) {
+    T unused[RO];
+    return column(k, gb, colr, colc, unused);
+  }
+  // The same, and cown[s] = M[row of slot s][k] for the rows this lane owns.
+  __device__ __forceinline__ T column(int k, T* gb, T (&colr)[BS], T (&colc)[BS],
+                                      T (&cown)[RO]) {
     const int kb = k / BS, kc = k - kb * BS;
     if (bj == kb) {
 #pragma unroll
@@ -129,6 +147,9 @@ struct QSym {
     for (int r = 0; r < BS; ++r) colr[r] = gb[(bi * BS + r) * BS + kc];
 #pragma unroll
     for (int c = 0; c < BS; ++c) colc[c] = gb[(bj * BS + c) * BS + kc];
+    // (a static select out of colr instead of these reads measured the same)
+#pragma unroll
+    for (int s = 0; s < RO; ++s) cown[s] = gb[(bi * BS + own_mrow(s)) * BS + kc];
     const T d = gb[k * BS + kc];
     lds_exchange();
     return d;
@@ -191,6 +212,30 @@ struct QSym {
     }
     lds_exchange();
   }
+
+  // The same on owned rows: the owners store w, every lane of a row block
+  // forms the block's BS sums (same products, same quad_sum) and keeps its own.
+  __device__ __forceinline__ void matvec_own(const T (&w)[RO], T* gb, T (&out)[RO]) {
+    T* wb = gb + CBUF;
+#pragma unroll
+    for (int s = 0; s < RO; ++s)
+      if (owns(s)) wb[bi * BS + own_row(s)] = w[s];
+    lds_exchange();
+    T wc[BS];
+#pragma unroll
+    for (int c = 0; c < BS; ++c) wc[c] = wb[bj * BS + c];
+#pragma unroll
+    for (int s = 0; s < RO; ++s) out[s] = T(0);
+#pragma unroll
+    for (int r = 0; r < BS; ++r) {
+      T s = T(0);
+#pragma unroll
+      for (int c = 0; c < BS; ++c) s = fma(m[r][c], wc[c], s);
+      s = quad_sum(s);
+      out[r / 4] = (bj == r % 4) ? s : out[r / 4];
+    }
+    lds_exchange();
+  }
 };
 
 // Per-group LDS block for the box active set: [Mat::BUF | f | lb | ub], the
@@ -225,18 +270,17 @@ __device__ __forceinline__ T bound_scale(T bnd) {
 // live = this group holds a real instance.  Returns the status code.
 // Bounds of this lane's rows and their violation scales, held in registers
 // for the whole solve (loop-invariant; the scan runs every iteration).
-template <typename T, int BS>
+template <typename T, int RO>
 struct QBounds {
-  T lo[BS], hi[BS], sl[BS], su[BS];
-  template <class Mat>
-  __device__ __forceinline__ void load(const Mat& M, const T* lbs, const T* ubs) {
+  T lo[RO], hi[RO], sl[RO], su[RO];
+  // mi: the rows of this lane's slots (RowOwn::mrow)
+  __device__ __forceinline__ void load(const int (&mi)[RO], const T* lbs, const T* ubs) {
 #pragma unroll
-    for (int r = 0; r < BS; ++r) {
-      const int i = M.bi * BS + r;
-      lo[r] = lbs[i];
-      hi[r] = ubs[i];
-      sl[r] = bound_scale(lo[r]);
-      su[r] = bound_scale(hi[r]);
+    for (int s = 0; s < RO; ++s) {
+      lo[s] = lbs[mi[s]];
+      hi[s] = ubs[mi[s]];
+      sl[s] = bound_scale(lo[s]);
+      su[s] = bound_scale(hi[s]);
     }
   }
 };
@@ -260,24 +304,184 @@ __device__ __forceinline__ void rows_argmin(const Sym2D<T, BS>&, T& v, int& idx)
   blocks_argmin(v, idx);
 }
 
-template <typename T, int BS, class Mat>
-__device__ __forceinline__ void qscan(const Mat& M, const int (&st)[BS], const T (&zr)[BS],
-                                      const QBounds<T, BS>& B, T& viol, int& pi, T& zv) {
+
+// One step of an arg-max / arg-min over DPP pattern CTRL; the same total
+// order as group_argmax / group_argmin (value, then the smaller index).
+template <int CTRL, typename T>
+__device__ __forceinline__ void dpp_argmax(T& v, int& idx, T& pay) {
+  const T ov = dpp<CTRL>(v);
+  const int oi = dpp<CTRL>(idx);
+  const T op = dpp<CTRL>(pay);
+  const bool take = (ov > v) || (ov == v && oi < idx);
+  v = take ? ov : v;
+  idx = take ? oi : idx;
+  pay = take ? op : pay;
+}
+template <int CTRL, typename T>
+__device__ __forceinline__ void dpp_argmin(T& v, int& idx) {
+  const T ov = dpp<CTRL>(v);
+  const int oi = dpp<CTRL>(idx);
+  const bool take = (ov < v) || (ov == v && oi < idx);
+  v = take ? ov : v;
+  idx = take ? oi : idx;
+}
+// value of lane J of the quad (quad_perm broadcast)
+template <int J, typename X>
+__device__ __forceinline__ X quad_lane(X v) {
+  return dpp<J | (J << 2) | (J << 4) | (J << 6)>(v);
+}
+
+// Row ownership: which lanes hold the row-indexed vectors of the box active
+// set (z, the multipliers, the states, the bounds and their scales).
+//   replicated  every lane of a row block holds all BS rows of the block and
+//               runs the scan, the ratio test and the updates over all of them
+//               (one QP per wave, Sym2D: 8 lanes per row block);
+//   owned       row r of a row block belongs to one lane (QSym: bj = r mod 4),
+//               RO = ceil(BS / 4) slots per lane; a slot without a row is
+//               padding (state 3, never a candidate, row() = -1).  Each row
+//               takes the arithmetic it takes replicated, on one lane instead
+//               of four, and the reductions run over all 16 lanes of the group
+//               with the same order (value, then the smaller index), so the
+//               results are the same bits.
+// Callers keep the replicated z / states at entry and exit: the owned policy
+// converts once per solve (deal() / gather()), the replicated one works on the
+// caller's arrays.
+// MPCQP_ROW_OWNER=0 builds the replicated layout everywhere (A/B).
+#ifndef MPCQP_ROW_OWNER
+#define MPCQP_ROW_OWNER 1
+#endif
+template <class Mat>
+struct QRowOwned {
+  static constexpr bool v = false;
+};
+// Owned at every BS.  At fp32 BS = 6 the compiler then spends more of the 256
+// registers of the kernels' two-wave launch bound (box_quad_kernel 167 -> 196
+// VGPRs, mpc_group_kernel 166..167 -> 191..192; the registers alone would have
+// allowed 3 waves) and is faster all the same: B = 4096, n = 22, us per launch,
+// replicated -> owned: nx = 2 nu = 1 68.1 -> 64.2, nx = 2 nu = 2 time-varying
+// 57.2 -> 54.0, nx = 4 nu = 1 84.0 -> 82.3, nx = 4 nu = 2 time-varying 73.6 ->
+// 70.0, mpcqp_solve_box 62.3 -> 57.9.
+template <typename T, int BS>
+struct QRowOwned<QSym<T, BS>> {
+  static constexpr bool v = MPCQP_ROW_OWNER != 0;
+};
+
+template <class Mat, bool OWN_ROWS = QRowOwned<Mat>::v>
+struct RowOwn {  // replicated
+  static constexpr bool OWNED = false;
+  static constexpr int BS = Mat::RPL;
+  static constexpr int RO = BS;
+  // slot s holds a row; its matrix row, to compare with a pivot (-1: none)
+  // and to address LDS
+  static __device__ __forceinline__ bool has(const Mat&, int) { return true; }
+  static __device__ __forceinline__ int row(const Mat& M, int s) { return M.bi * BS + s; }
+  static __device__ __forceinline__ int mrow(const Mat& M, int s) { return M.bi * BS + s; }
+  template <typename T>
+  static __device__ __forceinline__ void argmax(const Mat& M, T& v, int& idx, T& pay) {
+    rows_argmax(M, v, idx, pay);
+  }
+  template <typename T>
+  static __device__ __forceinline__ void argmin(const Mat& M, T& v, int& idx) {
+    rows_argmin(M, v, idx);
+  }
+  template <typename T>
+  static __device__ __forceinline__ T column(Mat& M, int k, T* gb, T (&colr)[BS],
+                                             T (&colc)[Mat::NC], T (&cown)[RO]) {
+    const T d = M.column(k, gb, colr, colc);
+#pragma unroll
+    for (int r = 0; r < BS; ++r) cown[r] = colr[r];
+    return d;
+  }
+  template <typename T>
+  static __device__ __forceinline__ void matvec(Mat& M, const T (&w)[RO], T* gb, T (&out)[RO]) {
+    M.matvec(w, gb, out);
+  }
+};
+
+template <class Mat>
+struct RowOwn<Mat, true> {  // owned (QSym)
+  static constexpr bool OWNED = true;
+  static constexpr int BS = Mat::RPL;
+  static constexpr int RO = Mat::RO;
+  static __device__ __forceinline__ bool has(const Mat& M, int s) { return M.owns(s); }
+  static __device__ __forceinline__ int row(const Mat& M, int s) {
+    return M.owns(s) ? M.bi * BS + M.own_row(s) : -1;
+  }
+  static __device__ __forceinline__ int mrow(const Mat& M, int s) {
+    return M.bi * BS + M.own_mrow(s);
+  }
+  template <typename X>
+  static __device__ __forceinline__ void deal(const Mat& M, const X (&full)[BS], X pad,
+                                              X (&own)[RO]) {
+#pragma unroll
+    for (int s = 0; s < RO; ++s) {
+      own[s] = pad;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (4 * s + j < BS) own[s] = (M.bj == j) ? full[4 * s + j] : own[s];
+    }
+  }
+  template <typename X>
+  static __device__ __forceinline__ void gather(const Mat&, const X (&own)[RO], X (&full)[BS]) {
+#pragma unroll
+    for (int r = 0; r < BS; ++r) {
+      const X v = own[r / 4];
+      full[r] = (r % 4 == 0)   ? quad_lane<0>(v)
+                : (r % 4 == 1) ? quad_lane<1>(v)
+                : (r % 4 == 2) ? quad_lane<2>(v)
+                               : quad_lane<3>(v);
+    }
+  }
+  // over the 4 owners of a row block, then over the 4 row blocks
+  template <typename T>
+  static __device__ __forceinline__ void argmax(const Mat&, T& v, int& idx, T& pay) {
+    dpp_argmax<0xB1>(v, idx, pay);
+    dpp_argmax<0x4E>(v, idx, pay);
+    group_argmax(v, idx, pay);
+  }
+  template <typename T>
+  static __device__ __forceinline__ void argmin(const Mat&, T& v, int& idx) {
+    dpp_argmin<0xB1>(v, idx);
+    dpp_argmin<0x4E>(v, idx);
+    group_argmin(v, idx);
+  }
+  template <typename T>
+  static __device__ __forceinline__ T column(Mat& M, int k, T* gb, T (&colr)[BS],
+                                             T (&colc)[Mat::NC], T (&cown)[RO]) {
+    return M.column(k, gb, colr, colc, cown);
+  }
+  template <typename T>
+  static __device__ __forceinline__ void matvec(Mat& M, const T (&w)[RO], T* gb, T (&out)[RO]) {
+    M.matvec_own(w, gb, out);
+  }
+};
+
+template <bool OWNED, class A, class B>
+__device__ __forceinline__ auto& own_or_full(A& own, B& full) {
+  if constexpr (OWNED) return own;
+  else return full;
+}
+
+// The most violated free row of a QP: ri = the rows of this lane's slots.
+// zv: its z.
+template <typename T, class Own, class Mat>
+__device__ __forceinline__ void qscan(const Mat& M, const int (&ri)[Own::RO],
+                                      const int (&st)[Own::RO], const T (&zr)[Own::RO],
+                                      const QBounds<T, Own::RO>& B, T& viol, int& pi, T& zv) {
   viol = -Lim<T>::inf();
   pi = 0;
   zv = T(0);
 #pragma unroll
-  for (int r = 0; r < BS; ++r) {
-    const int i = M.bi * BS + r;
+  for (int r = 0; r < Own::RO; ++r) {
     const T vl = (B.lo[r] - zr[r]) * B.sl[r];  // NaN for an infinite bound
     const T vu = (zr[r] - B.hi[r]) * B.su[r];
     const T v = (st[r] == 0) ? fmax(vl, vu) : -Lim<T>::inf();
     const bool take = v > viol;
     viol = take ? v : viol;
-    pi = take ? i : pi;
+    pi = take ? ri[r] : pi;
     zv = take ? zr[r] : zv;
   }
-  rows_argmax(M, viol, pi, zv);
+  Own::argmax(M, viol, pi, zv);
 }
 
 
@@ -286,35 +490,47 @@ __device__ __forceinline__ void qscan(const Mat& M, const int (&st)[BS], const T
 // equals -H^-1 swept back on the active rows); the active rows whose
 // multipliers have the wrong sign are released first (one sweep each), then
 // the active set runs as from a cold start.  st is returned either way.
-template <typename T, int BS, bool WARM, class Mat>
+template <typename T, int BS, bool WARM, class Mat, class Own = RowOwn<Mat>>
 __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lbs,
                                          const T* ubs, int n, int max_iter, T tol, bool live,
-                                         T (&zr)[BS], int& iters, int (&st)[BS] MPCQP_CLK_PARAM) {
-  QBounds<T, BS> B;
-  B.load(M, lbs, ubs);
-  T mu[BS];
+                                         T (&zfull)[BS], int& iters,
+                                         int (&stfull)[BS] MPCQP_CLK_PARAM) {
+  // z, the multipliers, the states and the bounds by owned slot (RowOwn)
+  constexpr int RO = Own::RO;
+  int ri[RO], mi[RO];
 #pragma unroll
-  for (int r = 0; r < BS; ++r) {
-    if constexpr (!WARM) st[r] = (M.bi * BS + r < n) ? 0 : 3;
+  for (int r = 0; r < RO; ++r) {
+    ri[r] = Own::row(M, r);
+    mi[r] = Own::mrow(M, r);
+  }
+  QBounds<T, RO> B;
+  B.load(mi, lbs, ubs);
+  // (replicated: the caller's arrays themselves)
+  T zown[Own::OWNED ? RO : 1], mu[RO];
+  int stown[Own::OWNED ? RO : 1];
+  auto& zr = own_or_full<Own::OWNED>(zown, zfull);
+  auto& st = own_or_full<Own::OWNED>(stown, stfull);
+  if constexpr (WARM && Own::OWNED) Own::deal(M, stfull, 3, stown);
+#pragma unroll
+  for (int r = 0; r < RO; ++r) {
+    if constexpr (!WARM) st[r] = (Own::has(M, r) && ri[r] < n) ? 0 : 3;
     mu[r] = T(0);
     zr[r] = T(0);
   }
   iters = 0;
   int code = MPCQP_STATUS_OPTIMAL;
   auto refresh = [&]() {
-    T w[BS], s[BS];
+    T w[RO], s[RO];
 #pragma unroll
-    for (int r = 0; r < BS; ++r) {
-      const int i = M.bi * BS + r;
+    for (int r = 0; r < RO; ++r) {
       const T zA = (st[r] == 1) ? B.lo[r] : ((st[r] == 2) ? B.hi[r] : T(0));
-      w[r] = (st[r] == 0) ? fs[i] : -zA;
+      w[r] = (st[r] == 0) ? fs[mi[r]] : -zA;
       zr[r] = zA;
     }
-    M.matvec(w, gb, s);
+    Own::matvec(M, w, gb, s);
 #pragma unroll
-    for (int r = 0; r < BS; ++r) {
-      const int i = M.bi * BS + r;
-      const T g = fs[i] - s[r];
+    for (int r = 0; r < RO; ++r) {
+      const T g = fs[mi[r]] - s[r];
       zr[r] = (st[r] == 0) ? s[r] : zr[r];
       mu[r] = (st[r] == 1) ? g : ((st[r] == 2) ? -g : T(0));
     }
@@ -328,13 +544,13 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
       T mv = Lim<T>::inf();
       int k = 0;
 #pragma unroll
-      for (int r = 0; r < BS; ++r) {
+      for (int r = 0; r < RO; ++r) {
         const bool a = (st[r] == 1 || st[r] == 2) && mu[r] < -tol;
         const bool take = a && mu[r] < mv;
         mv = take ? mu[r] : mv;
-        k = take ? (M.bi * BS + r) : k;
+        k = take ? ri[r] : k;
       }
-      rows_argmin(M, mv, k);
+      Own::argmin(M, mv, k);
       drop = drop && mv < Lim<T>::inf();
       if (!__any(drop)) break;
       if (drop && ++iters > max_iter) {
@@ -352,8 +568,8 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
       if (drop) {
         M.sweep_col(k, T(1), d, kr, kc);
 #pragma unroll
-        for (int r = 0; r < BS; ++r)
-          if (M.bi * BS + r == k) st[r] = 0;
+        for (int r = 0; r < RO; ++r)
+          if (ri[r] == k) st[r] = 0;
       }
       refresh();
     }
@@ -377,10 +593,10 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
           pi = a_pi;
           zv = a_zv;
         } else {
-          qscan<T, BS>(M, st, zr, B, viol, pi, zv);
+          qscan<T, Own>(M, ri, st, zr, B, viol, pi, zv);
         }
 #else
-        qscan<T, BS>(M, st, zr, B, viol, pi, zv);
+        qscan<T, Own>(M, ri, st, zr, B, viol, pi, zv);
 #endif
         if (active && need_p) {
           if (!(viol > tol)) {
@@ -405,29 +621,29 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
         stepping = false;
       }
       constexpr int NC = Mat::NC;  // columns per lane
-      T c[BS], cc[NC];
-      const T mpp = M.column(p, gb, c, cc);  // c[r] = M_ip, M_pp < 0
+      T c[BS], cc[NC], co[RO];  // c[r] = M_ip by block row, co by owned slot
+      const T mpp = Own::column(M, p, gb, c, cc, co);  // M_pp < 0
       const T rm = fast_rcp(mpp);
       const T sgn = (tgt > zp) ? T(1) : T(-1);
       const T t2 = fabs(tgt - zp);
       T ti = Lim<T>::inf();
       int k = 0;
 #pragma unroll
-      for (int r = 0; r < BS; ++r) {
-        const T cs = c[r] * rm;  // dz per unit move of z_p (c stays raw for the sweep)
+      for (int r = 0; r < RO; ++r) {
+        const T cs = co[r] * rm;  // dz per unit move of z_p (c stays raw for the sweep)
         const T dmu = ((st[r] == 1) ? -cs : ((st[r] == 2) ? cs : T(0))) * sgn;
         const bool cand = (st[r] == 1 || st[r] == 2) && dmu < T(0);
         const T t = cand ? -mu[r] * fast_rcp(dmu) : Lim<T>::inf();
         const bool take = t < ti;
         ti = take ? t : ti;
-        k = take ? (M.bi * BS + r) : k;
+        k = take ? ri[r] : k;
       }
-      rows_argmin(M, ti, k);
+      Own::argmin(M, ti, k);
       const bool partial = ti < t2;
       const T s_eff = stepping ? (partial ? ti : t2) : T(0);
 #pragma unroll
-      for (int r = 0; r < BS; ++r) {
-        const T cs = c[r] * rm;
+      for (int r = 0; r < RO; ++r) {
+        const T cs = co[r] * rm;
         const T dmu = ((st[r] == 1) ? -cs : ((st[r] == 2) ? cs : T(0))) * sgn;
         zr[r] = (st[r] == 0) ? fma(sgn * s_eff, cs, zr[r]) : zr[r];
         mu[r] = fma(s_eff, dmu, mu[r]);
@@ -457,8 +673,8 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
       // the sweep; used when the step was full (need_p)
       if (stepping && !bad) {
 #pragma unroll
-        for (int r = 0; r < BS; ++r) {
-          const int i = M.bi * BS + r;
+        for (int r = 0; r < RO; ++r) {
+          const int i = ri[r];
           if (partial && i == k) {
             st[r] = 0;
             mu[r] = T(0);
@@ -475,7 +691,7 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
         code = MPCQP_STATUS_NOT_CONVEX;
         active = false;
       }
-      qscan<T, BS>(M, st, zr, B, a_viol, a_pi, a_zv);
+      qscan<T, Own>(M, ri, st, zr, B, a_viol, a_pi, a_zv);
       have_scan = true;
       if (stepping && !bad) M.sweep_col(idx, sigma, d, kr, kcol);
       MPCQP_PHASE(7);
@@ -483,8 +699,8 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
       if (stepping && !bad) {
         M.sweep_col(idx, sigma, d, kr, kcol);
 #pragma unroll
-        for (int r = 0; r < BS; ++r) {
-          const int i = M.bi * BS + r;
+        for (int r = 0; r < RO; ++r) {
+          const int i = ri[r];
           if (partial && i == k) {
             st[r] = 0;
             mu[r] = T(0);
@@ -508,23 +724,27 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
     refresh();
     T viol, zv;
     int pi;
-    qscan<T, BS>(M, st, zr, B, viol, pi, zv);
+    qscan<T, Own>(M, ri, st, zr, B, viol, pi, zv);
     active = live && code == MPCQP_STATUS_OPTIMAL && viol > tol;
     if (!__any(active)) break;
   }
 #pragma unroll
-  for (int r = 0; r < BS; ++r) {
+  for (int r = 0; r < RO; ++r) {
     zr[r] = fmin(fmax(zr[r], B.lo[r]), B.hi[r]);
+  }
+  if constexpr (Own::OWNED) {
+    Own::gather(M, zown, zfull);
+    Own::gather(M, stown, stfull);
   }
   return code;
 }
 
-template <typename T, int BS, class Mat>
+template <typename T, int BS, class Mat, class Own = RowOwn<Mat>>
 __device__ __forceinline__ int gi_box(Mat& M, T* gb, const T* fs, const T* lbs,
                                            const T* ubs, int n, int max_iter, T tol, bool live,
                                            T (&zr)[BS], int& iters MPCQP_CLK_PARAM) {
   int st[BS];
-  return gi_box_st<T, BS, false>(M, gb, fs, lbs, ubs, n, max_iter, tol, live, zr, iters,
+  return gi_box_st<T, BS, false, Mat, Own>(M, gb, fs, lbs, ubs, n, max_iter, tol, live, zr, iters,
                                  st MPCQP_CLK_ARG);
 }
 

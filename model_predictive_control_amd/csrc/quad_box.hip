@@ -157,6 +157,15 @@ struct QMpcRows {
   static constexpr bool v = NX <= 2 && !(sizeof(T) == 8 && NU == 2 && BS <= 3);
 };
 
+// Row ownership of the box active set (RowOwn, quad.hpp) per instantiation.
+// fp64 NX = 4 NU = 2 BS = 5 sits at 256 VGPRs either way and its scratch would
+// grow from 52 to 56 bytes per lane: it keeps the replicated vectors.
+template <typename T, int NX, int NU, class Mat>
+struct QMpcOwned {
+  static constexpr bool v =
+      QRowOwned<Mat>::v && !(sizeof(T) == 8 && NX == 4 && NU == 2 && Mat::RPL == 5);
+};
+
 template <typename T, int NX, int NU, class Mat>
 struct QMpcLds {
   static constexpr bool ROWS = QMpcRows<T, NX, NU, Mat::RPL>::v;
@@ -844,8 +853,10 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
   else if ((__ballot(badbox) & gmask) != 0) code = MPCQP_STATUS_INFEASIBLE;
   T zr[RPL];
   int iters = 0;
-  const int c2 = gi_box<T, RPL>(M, gb, fs, lbs, ubs, n, a.max_iter, a.tol,
-                                     live && code == MPCQP_STATUS_OPTIMAL, zr, iters MPCQP_CLK_ARG);
+  using Own = RowOwn<Mat, QMpcOwned<T, NX, NU, Mat>::v>;
+  const int c2 = gi_box<T, RPL, Mat, Own>(M, gb, fs, lbs, ubs, n, a.max_iter, a.tol,
+                                          live && code == MPCQP_STATUS_OPTIMAL, zr,
+                                          iters MPCQP_CLK_ARG);
   if (code == MPCQP_STATUS_OPTIMAL) code = c2;
   MPCQP_PHASE(4);
 #ifdef MPCQP_PHASE_TIMING
