@@ -662,6 +662,50 @@ int mpcqp_mpc_poly_loop_soft(int dtype, int batch, int n, int m, int nbox, int n
                              int32_t* status, int max_iter, double tol, void* stream);
 
 /*
+ * mpcqp_mpc_poly_loop (rho = NULL) or mpcqp_mpc_poly_loop_soft with a per-step
+ * linear term g_t in the gradient and a per-step shift e_t of the row bounds,
+ * neither of which comes from the state: reference tracking with preview, a
+ * non-zero setpoint, a known affine term of the model.  Per step
+ *   z_t = argmin 1/2 z'Hz + (F x_t + g_t)'z  [+ the soft penalties]
+ *         s.t.  hl - E x_t - e_t <= G z <= hu - E x_t - e_t,  lbz <= z <= ubz
+ *   u_t = z_t[0..nu-1],  x_{t+1} = A x_t + B u_t (+ w_t)
+ * It is the one-launch counterpart of T calls of mpcqp_poly_solve with f1 =
+ * g_t (PolyQP.solve(f=)) and hl/hu moved by -e_t.  All arguments up to sigma
+ * and all outputs are those of mpcqp_mpc_poly_loop_soft.
+ * g: steps x batch x n (strideG = n), or steps x n shared by the batch
+ * (strideG = 0).  e: steps x batch x m (strideE = m) or steps x m (strideE =
+ * 0); the box rows are never shifted.  Either may be NULL; with both NULL the
+ * call is exactly mpcqp_mpc_poly_loop (rho = NULL) or mpcqp_mpc_poly_loop_soft,
+ * bit for bit.  When g is given a first kernel forms -Hinv g and -Ut g for all
+ * steps at once into scratch (scratch_bytes >=
+ * mpcqp_mpc_poly_loop_affine_workspace(dtype, batch, n, m, nbox, steps,
+ * g_shared = (strideG == 0)); for a shared g that product has only `steps`
+ * rows), and the loop adds them to s0 = L x_t and to the plan Kt'x_t; per step
+ * the loop reads m_total + nu more elements (n more when zs is requested).
+ * scratch is not read when g = NULL.  The call only enqueues on `stream` and
+ * allocates nothing.
+ * Status: as the loop without g and e; a non-finite entry of g_t or e_t gives
+ * NONFINITE at step t for that instance (and, as any failure, on its later
+ * steps); warm start, MPCQP_LOOP_COLD and the max_iter accounting are
+ * unchanged.
+ * Not supported: per-step input-box bounds (lbz/ubz stay fixed), g/e in
+ * mpcqp_mpc_box_loop, a matrix-core product for -Hinv g, references for the
+ * bicycle controllers.
+ */
+size_t mpcqp_mpc_poly_loop_affine_workspace(int dtype, int batch, int n, int m, int nbox,
+                                            int steps, int g_shared);
+int mpcqp_mpc_poly_loop_affine(int dtype, int batch, int n, int m, int nbox, int nx, int nu,
+                               int steps, int flags, const void* workspace, const void* E,
+                               const void* A, const void* Bm, const void* x0, int64_t strideX0,
+                               const void* hl, const void* hu, int64_t strideh,
+                               const void* lbz, const void* ubz, const void* w,
+                               const void* rho, const void* sigma,
+                               const void* g, int64_t strideG, const void* e, int64_t strideE,
+                               void* scratch, size_t scratch_bytes,
+                               void* xs, void* us, void* zs, void* ys, void* eps,
+                               int32_t* status, int max_iter, double tol, void* stream);
+
+/*
  * Batched finite-horizon Riccati recursion, FHC.py:51-61:
  *   K_k = -(R + B'P B)^{-1} B'P A,  P_k = Q + A'P A + A'P B K_k,  P_N = Pf
  * Outputs in the reference's order (lists reversed: K[0] is the first-stage

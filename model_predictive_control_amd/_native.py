@@ -94,6 +94,10 @@ SIGNATURES = {
                             [_i, _d, _vp]),
     "mpcqp_mpc_poly_loop_soft": (_i, [_i] * 9 + [_vp] * 5 + [_i64, _vp, _vp, _i64] + [_vp] * 11 +
                                  [_i, _d, _vp]),
+    "mpcqp_mpc_poly_loop_affine_workspace": (ctypes.c_size_t, [_i] * 7),
+    "mpcqp_mpc_poly_loop_affine": (_i, [_i] * 9 + [_vp] * 5 + [_i64, _vp, _vp, _i64] + [_vp] * 5 +
+                                   [_vp, _i64, _vp, _i64, _vp, ctypes.c_size_t] + [_vp] * 6 +
+                                   [_i, _d, _vp]),
     "mpcqp_mpc_qp_profile": (_i, [_i]),
     "mpcqp_mpc_qp_stage_ms": (_i, [ctypes.POINTER(ctypes.c_float)]),
     "mpcqp_bicycle_hessian": (_i, [_i, _i, _i, _d, ctypes.POINTER(ctypes.c_double), _i, _vp, _vp,

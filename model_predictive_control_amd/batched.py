@@ -24,7 +24,7 @@ import torch
 from . import _native as nat
 
 __all__ = [
-    "condense", "solve_box", "mpc_box", "mpc_box_loop", "mpc_poly_loop", "mpc_qp", "mpc_ipm", "solve_poly", "solve_qp", "sweep", "riccati", "gemv",
+    "condense", "solve_box", "mpc_box", "mpc_box_loop", "mpc_poly_loop", "tracking_terms", "mpc_qp", "mpc_ipm", "solve_poly", "solve_qp", "sweep", "riccati", "gemv",
     "rollout", "bicycle_rti", "bicycle_linearise", "bicycle_hessian", "bicycle_sqp_step",
     "pack_lower", "unpack_lower", "status_code", "status_iters", "workspace_bytes",
 ]
@@ -585,10 +585,16 @@ class PolyQP:
         nat.check(rc, "mpcqp_poly_solve")
         return z, y, status
 
+    def affine_scratch_bytes(self, batch: int, steps: int, g_shared: bool) -> int:
+        """Bytes of scratch ``loop(g=...)`` needs (``mpcqp_mpc_poly_loop_affine_workspace``)."""
+        return int(_lib().mpcqp_mpc_poly_loop_affine_workspace(
+            _code(self.dtype), int(batch), self.n, self.m, self.nbox, int(steps),
+            1 if g_shared else 0))
+
     def loop(self, A, B, x0, steps: int, hl=None, hu=None, E=None, w=None, *,
              plans: bool = False, multipliers: bool = False, cold: bool = False,
              max_iter: int = 0, tol: float = 0.0, out: dict | None = None,
-             soft: tuple | None = None, slacks: bool = False) -> dict:
+             soft: tuple | None = None, slacks: bool = False, g=None, e=None) -> dict:
         """The receding-horizon loop on this object's factors, ``steps`` steps
         in one launch (include/mpcqp.h ``mpcqp_mpc_poly_loop``): per step
         z_t = argmin 1/2 z'Hz + (F x_t)'z over hl - E x_t <= G z <= hu - E x_t,
@@ -606,7 +612,15 @@ class PolyQP:
         (``mpcqp_mpc_poly_loop_soft``); rho_i = inf keeps row i hard, the
         input box always is.  A step that ends with a slack > 0 carries
         ``STATUS_SOFTENED`` in its status word; with ``slacks`` eps (steps, b,
-        m) is returned too."""
+        m) is returned too.
+
+        ``g`` ((steps, n) shared by the batch, or (steps, b, n)) is a per-step
+        linear term: the step's gradient is F x_t + g_t (``tracking_terms``
+        builds it from a reference trajectory); ``e`` ((steps, m) or (steps,
+        b, m)) moves the bounds of the rows of G by -e_t.  With either the
+        call goes to ``mpcqp_mpc_poly_loop_affine``; its scratch (the products
+        -Hinv g, -Ut g of all steps) is allocated here or taken from
+        ``out["scratch"]`` (uint8, at least ``affine_scratch_bytes``)."""
         dt, dev, n, m, nx = self.dtype, self.device, self.n, self.m, self.nx
         if nx == 0:
             raise ValueError("PolyQP.loop needs the x0 -> gradient map F at construction")
@@ -639,6 +653,11 @@ class PolyQP:
         w = _dev(w, dt, dev)
         if w is not None and tuple(w.shape) != (T, batch, nx):
             raise ValueError(f"w must be ({T}, {batch}, {nx}), got {tuple(w.shape)}")
+        g, e = _dev(g, dt, dev), _dev(e, dt, dev)
+        for name, v, width in (("g", g, n), ("e", e, m)):
+            if v is not None and tuple(v.shape) not in ((T, width), (T, batch, width)):
+                raise ValueError(f"{name} must be ({T}, {width}) or ({T}, {batch}, {width}), "
+                                 f"got {tuple(v.shape)}")
         rho = sigma = None
         if soft is not None:
             if not isinstance(soft, (tuple, list)) or len(soft) != 2:
@@ -655,6 +674,17 @@ class PolyQP:
         elif slacks:
             raise ValueError("slacks=True needs soft=(rho, sigma)")
         o = dict(out or {})
+        scratch, sb = o.pop("scratch", None), 0
+        if g is not None:
+            sb = self.affine_scratch_bytes(batch, T, g.ndim == 2)
+            if scratch is None:
+                scratch = torch.empty((sb,), dtype=torch.uint8, device=dev)
+            elif (scratch.dtype != torch.uint8 or scratch.ndim != 1 or scratch.numel() < sb
+                  or scratch.device != x0.device):
+                raise ValueError(f"out['scratch'] must be a uint8 tensor of at least {sb} bytes "
+                                 f"on {dev}")
+            else:
+                sb = int(scratch.numel())
         shapes = dict(xs=((T + 1, batch, nx), dt), us=((T, batch, nu), dt),
                       status=((T, batch), torch.int32))
         if slacks:
@@ -668,6 +698,21 @@ class PolyQP:
                 o[k] = torch.empty(shp, dtype=kd, device=dev)
             elif tuple(o[k].shape) != shp or o[k].dtype != kd or not o[k].is_contiguous():
                 raise ValueError(f"out[{k!r}] must be a contiguous {kd} tensor of shape {shp}")
+        if g is not None or e is not None:
+            if rho is None or m == 0:
+                rho = sigma = None
+            rc = _lib().mpcqp_mpc_poly_loop_affine(
+                _code(dt), batch, n, m, self.nbox, nx, nu, T, nat.LOOP_COLD if cold else 0,
+                _ptr(self.ws), _ptr(E), _ptr(A), _ptr(B), _ptr(x0), nx, _ptr(hl), _ptr(hu), sh,
+                _ptr(self.lbz), _ptr(self.ubz), _ptr(w), _ptr(rho), _ptr(sigma),
+                _ptr(g), 0 if g is None or g.ndim == 2 else n,
+                _ptr(e), 0 if e is None or e.ndim == 2 else m, _ptr(scratch), sb,
+                _ptr(o["xs"]), _ptr(o["us"]), _ptr(o.get("zs")), _ptr(o.get("ys")),
+                _ptr(o.get("eps")), _ptr(o["status"]), int(max_iter), float(tol), _stream())
+            nat.check(rc, "mpcqp_mpc_poly_loop_affine")
+            if scratch is not None:
+                o["scratch"] = scratch
+            return o
         if rho is not None and m > 0:
             rc = _lib().mpcqp_mpc_poly_loop_soft(
                 _code(dt), batch, n, m, self.nbox, nx, nu, T, nat.LOOP_COLD if cold else 0,
@@ -687,10 +732,58 @@ class PolyQP:
         return o
 
 
+def tracking_terms(cd, Q, R, Qf, N: int, T: int, x_ref=None, u_ref=None):
+    """The per-step linear term g of ``PolyQP.loop`` for the tracking cost
+    sum_k (x_k - r_{t+k})'Q(x_k - r_{t+k}) + (u_k - ubar_{t+k})'R(u_k - ubar_{t+k})
+    (terminal weight Qf) of an MPC condensed as ``cd`` (a dict with Gam, (N*nx,
+    N*nu)):  g_t = -Gam' Qhat rbar_t - Rhat ubar_t  with Qhat = blkdiag(Q, ..,
+    Q, Qf), Rhat = blkdiag(R, .., R), rbar_t = x_ref[t+1 : t+N+1], ubar_t =
+    u_ref[t : t+N], both references indexed by absolute time: x_ref (nx,)
+    (a setpoint), (T+N+1, nx) or (b, T+N+1, nx); u_ref (nu,), (T+N, nu) or (b,
+    T+N, nu).  Returns g (T, n), or (T, b, n) when a reference is per instance.
+    Plain tensor algebra on the device of ``cd`` (CPU tensors work too)."""
+    Gam = cd["Gam"]
+    dt, dev = Gam.dtype, Gam.device
+    N, T = int(N), int(T)
+    n = int(Gam.shape[1])
+    nx, nu = int(Gam.shape[0]) // N, n // N
+    as_t = lambda v: torch.as_tensor(v, dtype=dt, device=dev)  # noqa: E731
+    if x_ref is None and u_ref is None:
+        raise ValueError("tracking_terms needs x_ref or u_ref")
+
+    def windows(ref, width, length, first, name):
+        """(T, N*width) or (b, T, N*width): the N-step windows from ``first``"""
+        r = as_t(ref)
+        if tuple(r.shape) == (width,):
+            r = r.expand(length, width)
+        if r.ndim not in (2, 3) or tuple(r.shape[-2:]) != (length, width):
+            raise ValueError(f"{name} must be ({width},), ({length}, {width}) or (b, {length}, "
+                             f"{width}), got {tuple(r.shape)}")
+        win = r[..., first:, :].unfold(-2, N, 1)[..., :T, :, :]     # (.., T, width, N)
+        return win.transpose(-1, -2).reshape(*r.shape[:-2], T, N * width)
+
+    parts, mats = [], []
+    if x_ref is not None:
+        Qhat = torch.block_diag(*([as_t(Q).reshape(nx, nx)] * (N - 1) + [as_t(Qf).reshape(nx, nx)]))
+        parts.append(windows(x_ref, nx, T + N + 1, 1, "x_ref"))
+        mats.append(Qhat.T @ Gam)                                    # (N*nx, n)
+    if u_ref is not None:
+        parts.append(windows(u_ref, nu, T + N, 0, "u_ref"))
+        mats.append(torch.block_diag(*([as_t(R).reshape(nu, nu)] * N)).T)
+    if len(parts) == 2 and parts[0].ndim != parts[1].ndim:
+        b = max(parts, key=lambda v: v.ndim).shape[0]
+        parts = [v if v.ndim == 3 else v.expand(b, *v.shape) for v in parts]
+    if len(parts) == 2 and parts[0].shape[:-1] != parts[1].shape[:-1]:
+        raise ValueError("x_ref and u_ref have different batch sizes")
+    g = -(torch.cat(parts, dim=-1) @ torch.cat(mats, dim=0))
+    return g.transpose(0, 1).contiguous() if g.ndim == 3 else g.contiguous()
+
+
 def mpc_poly_loop(A, B, Q, R, Qf, N: int, x0, xlo=None, xhi=None, lb=None, ub=None,
                   steps: int = 1, *, plant=None, w=None, plans: bool = False,
                   multipliers: bool = False, cold: bool = False, max_iter: int = 0,
-                  tol: float = 0.0, soft: tuple | None = None, slacks: bool = False) -> dict:
+                  tol: float = 0.0, soft: tuple | None = None, slacks: bool = False,
+                  x_ref=None, u_ref=None) -> dict:
     """The receding-horizon loop of the linear MPC with a state box on
     x_1..x_N and an input box (sessions 2 and 3, session_2/problem.py:4-33), on
     the device in one launch.  The shared model (A, B) is condensed once (H, F,
@@ -702,7 +795,9 @@ def mpc_poly_loop(A, B, Q, R, Qf, N: int, x0, xlo=None, xhi=None, lb=None, ub=No
     state box (``PolyQP.loop``): each a scalar, (nx,) per state component or
     (N*nx,) per row; ``slacks`` returns eps (steps, b, N*nx).  Returns the
     dict of ``PolyQP.loop`` plus ``condensed`` (H, F, Gam, Phi of the model,
-    unbatched)."""
+    unbatched).  ``x_ref`` / ``u_ref`` (shapes of ``tracking_terms``) make
+    the cost track a reference trajectory with preview instead of the origin;
+    the state and input boxes stay boxes on x and u."""
     dt = A.dtype if isinstance(A, torch.Tensor) else torch.float64
     dev = A.device if isinstance(A, torch.Tensor) else torch.device("cuda")
     A, B = _dev(A, dt, dev), _dev(B, dt, dev)
@@ -735,9 +830,13 @@ def mpc_poly_loop(A, B, Q, R, Qf, N: int, x0, xlo=None, xhi=None, lb=None, ub=No
         if not rows:
             raise ValueError("soft needs a state box (xlo or xhi)")
         soft = (stage_bound(soft[0], nx, "soft rho"), stage_bound(soft[1], nx, "soft sigma"))
+    g = None
+    if x_ref is not None or u_ref is not None:
+        g = tracking_terms(cd, _dev(Q, dt, dev), _dev(R, dt, dev), _dev(Qf, dt, dev), N, steps,
+                           x_ref, u_ref)
     o = qp.loop(Ap, Bp, x0, steps, hl, hu, cd["Phi"] if rows else None, w, plans=plans,
                 multipliers=multipliers, cold=cold, max_iter=max_iter, tol=tol, soft=soft,
-                slacks=slacks)
+                slacks=slacks, g=g)
     o["condensed"] = cd
     return o
 

@@ -205,7 +205,7 @@ def lti_box_mpc_loop(A, B, Q, R, Qf, N: int, X0, lb, ub, steps: int) -> dict:
 
 def lti_mpc_loop(problem, X0, steps: int, *, N: int | None = None, Qf=None, plant=None, w=None,
                  cold: bool = False, max_iter: int = 0, tol: float = 0.0,
-                 soft: tuple | None = None) -> dict:
+                 soft: tuple | None = None, x_ref=None, u_ref=None) -> dict:
     """The receding-horizon loop of the state- and input-constrained linear MPC
     of sessions 2 and 3 (session_2/problem.py:4-33) on a linear plant, all
     ``steps`` in one launch (``batched.mpc_poly_loop``).  ``problem`` is a
@@ -220,7 +220,11 @@ def lti_mpc_loop(problem, X0, steps: int, *, N: int | None = None, Qf=None, plan
     ``soft=(rho, sigma)`` (each a scalar, (nx,) or (N*nx,)) softens the state
     box with an exact penalty (``batched.mpc_poly_loop``) and adds slack (T, b,
     N, nx), by which the predicted state may leave the box, and softened (T,
-    b), whether any does; success stays "the step's code is 0"."""
+    b), whether any does; success stays "the step's code is 0".
+    ``x_ref`` ((nx,), (T+N+1, nx) or (b, T+N+1, nx)) and ``u_ref`` ((nu,),
+    (T+N, nu) or (b, T+N, nu)), indexed by absolute time, make the cost track a
+    reference with preview (``batched.tracking_terms``); with ``x_ref`` the
+    result has tracking_error (T, b, nx) = xs[1:] - x_ref[1:T+1]."""
     dev = torch.device("cuda")
     t = lambda a: None if a is None else torch.as_tensor(a, dtype=torch.float64, device=dev)  # noqa: E731
     if isinstance(problem, dict):
@@ -242,7 +246,7 @@ def lti_mpc_loop(problem, X0, steps: int, *, N: int | None = None, Qf=None, plan
         plant = (t(plant[0]), t(plant[1]))
     r = batched.mpc_poly_loop(A, B, Q, R, Qf, N, X0, t(xlo), t(xhi), lb, ub, T, plant=plant,
                               w=t(w), plans=True, cold=cold, max_iter=max_iter, tol=tol,
-                              soft=soft, slacks=soft is not None)
+                              soft=soft, slacks=soft is not None, x_ref=t(x_ref), u_ref=t(u_ref))
     cd = r["condensed"]
     xs, zs = r["xs"], r["zs"]
     pred = xs[:T] @ cd["Phi"].T + zs @ cd["Gam"].T                 # (T, b, N*nx)
@@ -254,4 +258,9 @@ def lti_mpc_loop(problem, X0, steps: int, *, N: int | None = None, Qf=None, plan
     if soft is not None:
         out["slack"] = r["eps"].reshape(T, b, N, nx)
         out["softened"] = (r["status"] & nat.STATUS_SOFTENED) != 0
+    if x_ref is not None:
+        xr = t(x_ref)
+        xr = xr[..., 1:T + 1, :] if xr.ndim > 1 else xr
+        out["tracking_error"] = xs[1:] - (xr.transpose(0, 1) if xr.ndim == 3 else
+                                          xr.unsqueeze(1) if xr.ndim == 2 else xr)
     return out

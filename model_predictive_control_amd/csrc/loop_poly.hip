@@ -40,6 +40,13 @@
 // with an exact penalty on a shared slack instead of a hard bound, as a third
 // row state inside the same active set (see poly_loop_kernel).
 // The hard instantiation compiles to what it was without the variant.
+//
+// mpcqp_mpc_poly_loop_affine is the AFFINE instantiation (hard or soft): a
+// per-step linear term g_t in the gradient and a shift e_t of the row bounds,
+// both independent of the state, so that -Hinv g and -Ut g are formed for all
+// steps at once by poly_affine_prep_kernel before the loop and the loop only
+// adds them.  AFFINE is a template flag like SOFT: the four
+// instantiations without it compile to what they were.
 #include "poly_ws.hpp"
 #include "sym2d.hpp"
 
@@ -79,8 +86,21 @@ struct PolyLoopSoftArgs : PolyLoopArgs<T> {
   const T* sigma;              // m, read where rho is finite
   T* eps;                      // steps x batch x m or null
 };
-template <typename T, bool SOFT>
-using PolyLoopArgsOf = std::conditional_t<SOFT, PolyLoopSoftArgs<T>, PolyLoopArgs<T>>;
+
+// mpcqp_mpc_poly_loop_affine: the products of poly_affine_prep_kernel and the
+// row shift.  Row (t, b) of zg / sg is t * gB + gmul * b (shared g: gB = 1,
+// gmul = 0), of e it is t * eB + emul * b.  rho is null in the hard instantiation.
+template <typename T>
+struct PolyLoopAffineArgs : PolyLoopSoftArgs<T> {
+  const T* zg;                 // R x n: -Hinv g, or null
+  const T* sg;                 // R x mt: -Ut g, or null
+  const T* e;                  // steps x (batch or 1) x m, or null
+  int gB, gmul, eB, emul;
+};
+template <typename T, bool SOFT, bool AFFINE = false>
+using PolyLoopArgsOf =
+    std::conditional_t<AFFINE, PolyLoopAffineArgs<T>,
+                       std::conditional_t<SOFT, PolyLoopSoftArgs<T>, PolyLoopArgs<T>>>;
 
 // LDS elements of the loop kernel: Sym2D scratch, the mat-vec partials, packed
 // M, L' and E' (nx x NMAX each, transposed: lane = row reads conflict-free),
@@ -95,10 +115,11 @@ __host__ __device__ inline int poly_loop_lds(int BS, int mt, int nx, int nu) {
 // epilogue of dual_range_kernel.  One function for the plan (global Ut, Kt)
 // and for the applied input (their LDS copies), so that u_t equals z_t[0..nu)
 // bit for bit.
+// z0: the state-independent part of the plan (-Hinv g_t)_j, 0 without one.
 template <typename T>
 __device__ __forceinline__ T poly_epilogue(const T* Kt, const T* Ut, int64_t ld, int j, int nx,
-                                           const T* x, T yi, uint64_t yact) {
-  T acc = T(0);
+                                           const T* x, T yi, uint64_t yact, T z0 = T(0)) {
+  T acc = z0;
   for (int k = 0; k < nx; ++k) acc = fma(Kt[(int64_t)k * ld + j], x[k], acc);
   for (uint64_t mk = yact; mk; mk &= mk - 1) {
     const int r = uniform(__builtin_ctzll(mk));
@@ -117,8 +138,11 @@ __device__ __forceinline__ T poly_epilogue(const T* Kt, const T* Ut, int64_t ld,
 // active row of the problem with M_ii + 1/sigma on its diagonal and the bound
 // moved by -sgn rho/sigma, so W is SWEEP_A of that matrix and a regime switch
 // of an active row is a rank-one update of W (Sym2D::update_col).
-template <typename T, int BS, bool SOFT>
-__global__ __launch_bounds__(64) void poly_loop_kernel(PolyLoopArgsOf<T, SOFT> a) {
+//
+// AFFINE: a is a PolyLoopAffineArgs; per step the row's lane adds sg to s0,
+// moves the bounds of the rows < m by -e_t, and the epilogue starts from zg.
+template <typename T, int BS, bool SOFT, bool AFFINE = false>
+__global__ __launch_bounds__(64) void poly_loop_kernel(PolyLoopArgsOf<T, SOFT, AFFINE> a) {
   using S2 = Sym2D<T, BS>;
   constexpr int NMAX = S2::NMAX;
   static_assert(NMAX <= kWave, "one row per lane");
@@ -218,6 +242,8 @@ __global__ __launch_bounds__(64) void poly_loop_kernel(PolyLoopArgsOf<T, SOFT> a
     // record x_t; the step's disturbance; s0 = L x_t, the rows' shift E x_t
     T wv = T(0);
     bool nf = false;
+    int64_t rg = 0;  // AFFINE: the step's row of zg / sg
+    if constexpr (AFFINE) rg = (int64_t)t * a.gB + (int64_t)a.gmul * b;
     if (lane < nx) {
       const T xv = xl[lane];
       a.xs[tb * nx + lane] = xv;
@@ -233,7 +259,18 @@ __global__ __launch_bounds__(64) void poly_loop_kernel(PolyLoopArgsOf<T, SOFT> a
       }
       nf |= !finite(s0) || !finite(ex);
     }
-    const T lt = li - ex, ut = ui - ex;
+    T lt = li - ex, ut = ui - ex;
+    if constexpr (AFFINE) {
+      // loaded here, not ahead of the L x_t products: two values less in flight
+      // keep the BS = 2 hard instantiation at 4 waves per SIMD (126 VGPRs, not 130)
+      T sgv = T(0), ev = T(0);
+      if (a.sg && row) sgv = a.sg[rg * mt + lane];
+      if (a.e && lane < m) ev = a.e[((int64_t)t * a.eB + (int64_t)a.emul * b) * m + lane];
+      nf |= !finite(sgv) || !finite(ev);
+      s0 += sgv;
+      lt -= ev;
+      ut -= ev;
+    }
     // relative-violation scales 1/(1+|bound|), NaN for an infinite bound (a NaN
     // violation never wins the arg-max)
     const T sl = finite(lt) ? T(1) / (T(1) + fabs(lt)) : T(__builtin_nan(""));
@@ -516,7 +553,11 @@ __global__ __launch_bounds__(64) void poly_loop_kernel(PolyLoopArgsOf<T, SOFT> a
     // the applied input from the LDS columns; the plan from the global factors
     {
       const int j = lane < nu ? lane : 0;
-      const T uv = poly_epilogue<T>(Kn, Un, nu, j, nx, xl, yi, yact);
+      T z0 = T(0);
+      if constexpr (AFFINE) {
+        if (a.zg) z0 = a.zg[rg * nz + j];
+      }
+      const T uv = poly_epilogue<T>(Kn, Un, nu, j, nx, xl, yi, yact, z0);
       if (lane < nu) {
         const T uo = okc ? uv : T(__builtin_nan(""));
         ul[lane] = uo;
@@ -526,7 +567,11 @@ __global__ __launch_bounds__(64) void poly_loop_kernel(PolyLoopArgsOf<T, SOFT> a
     if (a.zs) {
       for (int j0 = 0; j0 < nz; j0 += kWave) {
         const int j = j0 + lane;
-        const T zv = poly_epilogue<T>(a.Kt, a.Ut, nz, j < nz ? j : 0, nx, xl, yi, yact);
+        T z0 = T(0);
+        if constexpr (AFFINE) {
+          if (a.zg) z0 = a.zg[rg * nz + (j < nz ? j : 0)];
+        }
+        const T zv = poly_epilogue<T>(a.Kt, a.Ut, nz, j < nz ? j : 0, nx, xl, yi, yact, z0);
         if (j < nz) a.zs[tb * nz + j] = okc ? zv : T(__builtin_nan(""));
       }
     }
@@ -574,41 +619,121 @@ __global__ __launch_bounds__(64) void poly_loop_kernel(PolyLoopArgsOf<T, SOFT> a
   if (lane < nx) a.xs[((int64_t)a.steps * a.batch + b) * nx + lane] = xl[lane];
 }
 
-template <typename T, int BS, bool SOFT>
-static int launch_poly_loop(const PolyLoopArgsOf<T, SOFT>& a, hipStream_t st) {
+// zg = -Hinv g (R x n) and sg = -Ut g (R x mt) for the R rows of g: the
+// state-independent products of every step of mpcqp_mpc_poly_loop_affine, a
+// skinny GEMM [R x n] . [n x (n + mt)].  A workgroup takes kPrepRows rows of g,
+// staged kPrepK columns at a time in LDS; a thread owns one output column (a
+// column of Hinv, read along its contiguous rows since Hinv is symmetric, or a
+// row of Ut, staged through LDS so that the global read runs along k) and
+// keeps one accumulator per tile row: an element of Hinv / Ut is loaded once
+// per tile and used kPrepRows times from its register.  No atomics; every
+// output element has one writer.
+constexpr int kPrepRows = 16, kPrepK = 32, kPrepThreads = 256;
+
+template <typename T>
+__global__ __launch_bounds__(kPrepThreads) void poly_affine_prep_kernel(
+    const T* __restrict__ g, int64_t R, int n, int mt, const T* __restrict__ Hinv,
+    const T* __restrict__ Ut, T* __restrict__ zg, T* __restrict__ sg) {
+  __shared__ T gs[kPrepRows][kPrepK];
+  __shared__ T uts[kWave][kPrepK + 1];  // +1: lane = row reads hit distinct banks
+  const int tid = threadIdx.x;
+  const int64_t r0 = (int64_t)blockIdx.x * kPrepRows;
+  for (int c0 = 0; c0 < n + mt; c0 += kPrepThreads) {
+    const int c = c0 + tid;
+    const bool ucols = c0 + kPrepThreads > n;  // this block of columns reaches into Ut
+    T acc[kPrepRows];
+#pragma unroll
+    for (int i = 0; i < kPrepRows; ++i) acc[i] = T(0);
+    for (int k0 = 0; k0 < n; k0 += kPrepK) {
+      const int kc = min(kPrepK, n - k0);
+      __syncthreads();
+      for (int e = tid; e < kPrepRows * kPrepK; e += kPrepThreads) {
+        const int i = e / kPrepK, kk = e - i * kPrepK;
+        gs[i][kk] = (r0 + i < R && kk < kc) ? g[(r0 + i) * n + k0 + kk] : T(0);
+      }
+      if (ucols) {
+        for (int e = tid; e < mt * kPrepK; e += kPrepThreads) {
+          const int r = e / kPrepK, kk = e - r * kPrepK;
+          uts[r][kk] = kk < kc ? Ut[(int64_t)r * n + k0 + kk] : T(0);
+        }
+      }
+      __syncthreads();
+      if (c < n) {
+        for (int kk = 0; kk < kc; ++kk) {
+          const T h = Hinv[(int64_t)(k0 + kk) * n + c];
+#pragma unroll
+          for (int i = 0; i < kPrepRows; ++i) acc[i] = fma(h, gs[i][kk], acc[i]);
+        }
+      } else if (c < n + mt) {
+        for (int kk = 0; kk < kc; ++kk) {
+          const T h = uts[c - n][kk];
+#pragma unroll
+          for (int i = 0; i < kPrepRows; ++i) acc[i] = fma(h, gs[i][kk], acc[i]);
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < kPrepRows; ++i) {
+      if (r0 + i < R) {
+        if (c < n) zg[(r0 + i) * n + c] = -acc[i];
+        else if (c < n + mt) sg[(r0 + i) * mt + (c - n)] = -acc[i];
+      }
+    }
+  }
+}
+
+// Scratch of mpcqp_mpc_poly_loop_affine: zg, then sg.
+struct PolyAffineWs {
+  int64_t R, oZg, oSg, total;
+};
+static inline PolyAffineWs poly_affine_ws(size_t es, int batch, int n, int mt, int steps,
+                                          bool shared) {
+  PolyAffineWs w;
+  w.R = (int64_t)steps * (shared ? 1 : batch);
+  w.oZg = 0;
+  w.oSg = align256(w.R * n * (int64_t)es);
+  w.total = align256(w.oSg + w.R * mt * (int64_t)es);
+  return w;
+}
+
+template <typename T, int BS, bool SOFT, bool AFFINE>
+static int launch_poly_loop(const PolyLoopArgsOf<T, SOFT, AFFINE>& a, hipStream_t st) {
   const size_t bytes = (size_t)poly_loop_lds(BS, a.mt, a.nx, a.nu) * sizeof(T);
   if (bytes > 64 * 1024) {
     set_error("mpcqp_mpc_poly_loop: %zu B of LDS needed, 65536 available", bytes);
     return MPCQP_ENOTSUP;
   }
-  hipLaunchKernelGGL((poly_loop_kernel<T, BS, SOFT>), dim3((unsigned)a.batch), dim3(kWave), bytes,
-                     st, a);
+  hipLaunchKernelGGL((poly_loop_kernel<T, BS, SOFT, AFFINE>), dim3((unsigned)a.batch),
+                     dim3(kWave), bytes, st, a);
   MPCQP_CHECK_LAUNCH("poly_loop_kernel");
   return MPCQP_OK;
 }
 
-template <typename T, bool SOFT>
-static int poly_loop_t(const PolyLoopArgsOf<T, SOFT>& a, hipStream_t st) {
+template <typename T, bool SOFT, bool AFFINE = false>
+static int poly_loop_t(const PolyLoopArgsOf<T, SOFT, AFFINE>& a, hipStream_t st) {
   switch ((a.mt + 7) / 8) {
-    case 1: return launch_poly_loop<T, 1, SOFT>(a, st);
-    case 2: return launch_poly_loop<T, 2, SOFT>(a, st);
-    case 3: return launch_poly_loop<T, 3, SOFT>(a, st);
-    case 4: return launch_poly_loop<T, 4, SOFT>(a, st);
-    case 5: return launch_poly_loop<T, 5, SOFT>(a, st);
-    case 6: return launch_poly_loop<T, 6, SOFT>(a, st);
-    case 7: return launch_poly_loop<T, 7, SOFT>(a, st);
-    default: return launch_poly_loop<T, 8, SOFT>(a, st);
+    case 1: return launch_poly_loop<T, 1, SOFT, AFFINE>(a, st);
+    case 2: return launch_poly_loop<T, 2, SOFT, AFFINE>(a, st);
+    case 3: return launch_poly_loop<T, 3, SOFT, AFFINE>(a, st);
+    case 4: return launch_poly_loop<T, 4, SOFT, AFFINE>(a, st);
+    case 5: return launch_poly_loop<T, 5, SOFT, AFFINE>(a, st);
+    case 6: return launch_poly_loop<T, 6, SOFT, AFFINE>(a, st);
+    case 7: return launch_poly_loop<T, 7, SOFT, AFFINE>(a, st);
+    default: return launch_poly_loop<T, 8, SOFT, AFFINE>(a, st);
   }
 }
 
-// Both entry points: rho == nullptr is the hard loop.
+// All three entry points: rho == nullptr is the hard loop; g == e == nullptr
+// launches the kernels of the first two.
 static int poly_loop_entry(const char* who, int dtype, int batch, int n, int m, int nbox, int nx,
                            int nu, int steps, int flags, const void* workspace, const void* E,
                            const void* A, const void* Bm, const void* x0, int64_t strideX0,
                            const void* hl, const void* hu, int64_t strideh, const void* lbz,
                            const void* ubz, const void* w, const void* rho, const void* sigma,
                            void* xs, void* us, void* zs, void* ys, void* eps, int32_t* status,
-                           int max_iter, double tol, void* stream) {
+                           int max_iter, double tol, void* stream, const void* g = nullptr,
+                           int64_t strideG = 0, const void* e = nullptr, int64_t strideE = 0,
+                           void* scratch = nullptr, size_t scratch_bytes = 0) {
   MPCQP_CHECK_ARG(dtype == MPCQP_F64 || dtype == MPCQP_F32, "%s: bad dtype %d", who, dtype);
   MPCQP_CHECK_ARG(batch >= 0 && n >= 1 && m >= 0 && steps >= 0,
                   "%s: bad sizes batch=%d n=%d m=%d steps=%d", who, batch, n, m, steps);
@@ -621,8 +746,17 @@ static int poly_loop_entry(const char* who, int dtype, int batch, int n, int m, 
   MPCQP_CHECK_ARG(strideX0 >= 0 && strideh >= 0, "%s: negative stride", who);
   MPCQP_CHECK_ARG(!nbox || lbz || ubz, "%s: nbox set without lbz/ubz", who);
   MPCQP_CHECK_ARG(!rho || sigma, "%s: rho given without sigma", who);
-  if (batch == 0) return MPCQP_OK;
+  MPCQP_CHECK_ARG(strideG >= 0 && strideE >= 0, "%s: negative stride", who);
+  MPCQP_CHECK_ARG(!g || strideG == 0 || strideG == n, "%s: strideG=%lld is neither 0 nor n=%d",
+                  who, (long long)strideG, n);
+  MPCQP_CHECK_ARG(!e || strideE == 0 || strideE == m, "%s: strideE=%lld is neither 0 nor m=%d",
+                  who, (long long)strideE, m);
   const int mt = m + (nbox ? n : 0);
+  const PolyAffineWs S = poly_affine_ws(dtype_size(dtype), batch, n, mt, steps, strideG == 0);
+  MPCQP_CHECK_ARG(!g || S.total == 0 || (scratch && scratch_bytes >= (size_t)S.total),
+                  "%s: g needs %lld B of scratch, %zu given", who, (long long)S.total,
+                  scratch ? scratch_bytes : (size_t)0);
+  if (batch == 0) return MPCQP_OK;
   const PolyWs L = poly_ws(dtype_size(dtype), n, mt, nx);
   const char* base = (const char*)workspace;
   auto fill = [&](auto& a, auto tp) {
@@ -644,6 +778,28 @@ static int poly_loop_entry(const char* who, int dtype, int batch, int n, int m, 
   auto run = [&](auto tp) {
     using T = decltype(tp);
     hipStream_t st = (hipStream_t)stream;
+    if ((g || (e && m > 0)) && steps > 0) {
+      PolyLoopAffineArgs<T> a;
+      fill(a, tp);
+      a.rho = (const T*)rho; a.sigma = (const T*)sigma; a.eps = rho ? (T*)eps : nullptr;
+      a.zg = a.sg = nullptr;
+      a.gB = strideG == 0 ? 1 : batch; a.gmul = strideG == 0 ? 0 : 1;
+      a.e = m > 0 ? (const T*)e : nullptr;
+      a.eB = strideE == 0 ? 1 : batch; a.emul = strideE == 0 ? 0 : 1;
+      if (g) {
+        T* zg = (T*)((char*)scratch + S.oZg);
+        T* sg = (T*)((char*)scratch + S.oSg);
+        const int64_t blocks = (S.R + kPrepRows - 1) / kPrepRows;
+        MPCQP_CHECK_ARG(blocks <= 0x7fffffff, "%s: %lld rows of g exceed the grid", who,
+                        (long long)S.R);
+        hipLaunchKernelGGL((poly_affine_prep_kernel<T>), dim3((unsigned)blocks),
+                           dim3(kPrepThreads), 0, st, (const T*)g, S.R, n, mt,
+                           (const T*)(base + L.oHinv), (const T*)(base + L.oUt), zg, sg);
+        MPCQP_CHECK_LAUNCH("poly_affine_prep_kernel");
+        a.zg = zg; a.sg = sg;
+      }
+      return rho ? poly_loop_t<T, true, true>(a, st) : poly_loop_t<T, false, true>(a, st);
+    }
     if (rho) {
       PolyLoopSoftArgs<T> a;
       fill(a, tp);
@@ -685,4 +841,27 @@ extern "C" int mpcqp_mpc_poly_loop_soft(int dtype, int batch, int n, int m, int 
                                 steps, flags, workspace, E, A, Bm, x0, strideX0, hl, hu, strideh,
                                 lbz, ubz, w, rho, sigma, xs, us, zs, ys, eps, status, max_iter, tol,
                                 stream);
+}
+
+extern "C" size_t mpcqp_mpc_poly_loop_affine_workspace(int dtype, int batch, int n, int m, int nbox,
+                                                       int steps, int g_shared) {
+  if ((dtype != MPCQP_F64 && dtype != MPCQP_F32) || batch < 0 || n < 1 || m < 0 || steps < 0)
+    return 0;
+  return (size_t)mpcqp::poly_affine_ws(mpcqp::dtype_size(dtype), batch, n, m + (nbox ? n : 0),
+                                       steps, g_shared != 0)
+      .total;
+}
+
+extern "C" int mpcqp_mpc_poly_loop_affine(
+    int dtype, int batch, int n, int m, int nbox, int nx, int nu, int steps, int flags,
+    const void* workspace, const void* E, const void* A, const void* Bm, const void* x0,
+    int64_t strideX0, const void* hl, const void* hu, int64_t strideh, const void* lbz,
+    const void* ubz, const void* w, const void* rho, const void* sigma, const void* g,
+    int64_t strideG, const void* e, int64_t strideE, void* scratch, size_t scratch_bytes, void* xs,
+    void* us, void* zs, void* ys, void* eps, int32_t* status, int max_iter, double tol,
+    void* stream) {
+  return mpcqp::poly_loop_entry("mpcqp_mpc_poly_loop_affine", dtype, batch, n, m, nbox, nx, nu,
+                                steps, flags, workspace, E, A, Bm, x0, strideX0, hl, hu, strideh,
+                                lbz, ubz, w, rho, sigma, xs, us, zs, ys, eps, status, max_iter, tol,
+                                stream, g, strideG, e, strideE, scratch, scratch_bytes);
 }

@@ -26,6 +26,18 @@ JSON line (and appends it to --json).
   3. (session-2 batch only) Problem(u_min=-2.0), x0 drawn the same way: the
      soft loop with (50, 1) -- rate, share of softened steps, iterations --
      and the hard loop on it -- rate, share of dead (instance, step) pairs.
+
+  python tools/poly_loop_rate.py --affine [--config4] [--ab-lib OTHER.so] ...
+
+--affine measures the loop with a per-step linear term (mpcqp_mpc_poly_loop_affine):
+  (i)   the hard warm loop of this build and of --ab-lib, alternately, as --soft does;
+  (ii)  the new entry point with a g shared by the batch: a ramp reference on
+        the first state, through batched.tracking_terms;
+  (iii) the same values as a per-instance g (steps x batch x n): the same loop
+        iterations, so that (iii) - (ii) is what the batch-sized product -Hinv g,
+        -Ut g (the prep kernel) and the per-instance reads cost;
+  (iv)  the per-step path with the same term: T x (PolyQP.solve(x, f=g_t, out=)
+        + the row-bound update + the torch plant) in one HIP graph.
 """
 import argparse
 import ctypes
@@ -197,10 +209,136 @@ def soft_mode(a, dev):
     return res
 
 
+def _ab_hard(a, p, T, dev, res):
+    """The hard warm loop of this build and, with --ab-lib, of another build,
+    timed alternately: the median of each round."""
+    b, nx, nu = a.batch, p["A"].shape[0], p["B"].shape[1]
+    libs = {"this": nat.load()}
+    if a.ab_lib:
+        libs["other"] = ctypes.CDLL(os.path.abspath(a.ab_lib))
+    outs = {k: _outs(b, T, nx, nu, dev) for k in libs}
+    calls = {k: _hard_loop_call(lib, p, T, outs[k]) for k, lib in libs.items()}
+    med = {k: [] for k in libs}
+    for _ in range(a.rounds):
+        for k in libs:
+            med[k].append(_median_ms(calls[k], a.warmup, a.repeats)[0])
+    for k in libs:
+        res[f"hard_{k}_round_medians_ms"] = med[k]
+        res[f"hard_{k}_ms"] = float(np.median(med[k]))
+        res[f"hard_{k}_steps_per_s"] = b * T / (res[f"hard_{k}_ms"] * 1e-3)
+    if a.ab_lib:
+        res["hard_outputs_equal"] = all(
+            np.array_equal(outs["this"][k].cpu().numpy(), outs["other"][k].cpu().numpy(),
+                           equal_nan=k != "status") for k in ("xs", "us", "status"))
+    res["hard"] = _stats(outs["this"])
+    return outs["this"]
+
+
+def affine_mode(a, dev):
+    b, T = a.batch, a.steps
+    rate = lambda ms: b * T / (ms * 1e-3)  # noqa: E731
+    p = _config4(b, dev) if a.config4 else _session2(b, dev)
+    qp, A, B, x0, hl, hu, E = (p[k] for k in ("qp", "A", "B", "x0", "hl", "hu", "E"))
+    nx, nu, n = A.shape[0], B.shape[1], qp.n
+    N = n // nu
+    f64 = dict(dtype=torch.float64, device=dev)
+    res = dict(tool="poly_loop_rate", mode="affine", problem=p["name"], batch=b, steps=T, n=n,
+               m_total=qp.mt, repeats=a.repeats, rounds=a.rounds)
+    _ab_hard(a, p, T, dev, res)                                            # (i)
+
+    # the reference: a ramp on the first state that levels off, the rest at 0
+    if a.config4:
+        Q, R = torch.eye(nx, **f64), 0.1 * torch.eye(nu, **f64)
+        ramp = np.minimum(0.05 * np.arange(T + N + 1), 1.0)
+    else:
+        pr = Problem()
+        Q, R = (torch.as_tensor(np.asarray(v, float), **f64) for v in (pr.Q, pr.R))
+        ramp = np.minimum(-40.0 + 6.0 * np.arange(T + N + 1), 0.0)
+    cd = batched.condense(A, B, Q, R, Q, N, outputs=("H", "Gam"))
+    x_ref = torch.zeros((T + N + 1, nx), **f64)
+    x_ref[:, 0] = torch.as_tensor(ramp, **f64)
+    g = batched.tracking_terms({"Gam": cd["Gam"][0]}, Q, R, Q, N, T, x_ref)   # (T, n)
+    gb = g[:, None].expand(T, b, n).contiguous()
+
+    def loop_run(gg):
+        # a direct call like the hard loop's, so that both are timed alike
+        o = _outs(b, T, nx, nu, dev)
+        sb = qp.affine_scratch_bytes(b, T, gg.ndim == 2)
+        scratch = torch.empty((sb,), dtype=torch.uint8, device=dev)
+        ptr = batched._ptr
+        lib = nat.load()
+        args = (nat.F64, b, n, qp.m, qp.nbox, nx, nu, T, 0, ptr(qp.ws), ptr(E), ptr(A), ptr(B),
+                ptr(x0), nx, ptr(hl), ptr(hu), 0, ptr(qp.lbz), ptr(qp.ubz), None, None, None,
+                ptr(gg), 0 if gg.ndim == 2 else n, None, 0, ptr(scratch), sb, ptr(o["xs"]),
+                ptr(o["us"]), None, None, None, ptr(o["status"]), 0, 0.0, batched._stream())
+
+        def fn():
+            rc = lib.mpcqp_mpc_poly_loop_affine(*args)
+            assert rc == 0, rc
+        ms = _median_ms(fn, a.warmup, a.repeats)[0]
+        return o, dict(ms=ms, steps_per_s=rate(ms), ms_over_hard=ms / res["hard_this_ms"],
+                       **_stats(o))
+
+    o_sh, res["affine_shared_g"] = loop_run(g)                             # (ii)
+    o_pi, res["affine_per_instance_g"] = loop_run(gb)                      # (iii)
+    res["shared_equals_per_instance"] = all(
+        np.array_equal(o_sh[k].cpu().numpy(), o_pi[k].cpu().numpy(), equal_nan=k != "status")
+        for k in ("xs", "us", "status"))
+    extra = res["affine_per_instance_g"]["ms"] - res["affine_shared_g"]["ms"]
+    res["per_instance_prep_ms"] = extra
+    res["per_instance_prep_share"] = extra / res["affine_per_instance_g"]["ms"]
+    res["prep_macs_per_step"] = (n + qp.mt) * n
+
+    # (iv) the per-step path with f = g_t, T steps in one HIP graph
+    xs = torch.empty((T + 1, b, nx), **f64)
+    zs = torch.empty((T, b, n), **f64)
+    y = torch.empty((b, qp.mt), **f64)
+    st = torch.empty((T, b), dtype=torch.int32, device=dev)
+    hlt = None if hl is None or E is None else torch.empty((b, qp.m), **f64)
+    hut = None if hu is None or E is None else torch.empty((b, qp.m), **f64)
+    Et = None if E is None else E.T.contiguous()
+    At, Bt = A.T.contiguous(), B.T.contiguous()
+    tmp = torch.empty((b, nx), **f64)
+
+    def episode():
+        xs[0].copy_(x0)
+        for t in range(T):
+            x = xs[t]
+            if Et is not None:
+                torch.addmm(hl, x, Et, alpha=-1.0, out=hlt)
+                torch.addmm(hu, x, Et, alpha=-1.0, out=hut)
+                qp.solve(x, g[t], hlt, hut, out=(zs[t], y, st[t]))
+            else:
+                qp.solve(x, g[t], hl, hu, out=(zs[t], y, st[t]))
+            torch.mm(x, At, out=tmp)
+            torch.addmm(tmp, zs[t, :, :nu], Bt, out=xs[t + 1])
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        episode()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        episode()
+    ms_step = _median_ms(graph.replay, a.warmup, a.repeats)[0]
+    torch.cuda.synchronize()
+    both = (((o_sh["status"] & 0xFF) == 0) & ((st & 0xFF) == 0)).all(dim=0)
+    res["per_step_graph"] = dict(
+        ms=ms_step, steps_per_s=rate(ms_step),
+        optimal_fraction=((st & 0xFF) == 0).double().mean().item(),
+        max_abs_x_diff_vs_loop=((o_sh["xs"][:, both] - xs[:, both]).abs().max().item()
+                                if both.any() else float("nan")))
+    res["speedup_shared_g_vs_per_step"] = ms_step / res["affine_shared_g"]["ms"]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config4", action="store_true")
     ap.add_argument("--soft", action="store_true")
+    ap.add_argument("--affine", action="store_true")
     ap.add_argument("--ab-lib", default=None)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--horizon", type=int, default=None, help="--soft: N of the session-2 problem")
@@ -212,8 +350,8 @@ def main():
     a = ap.parse_args()
     assert a.repeats >= 10
     dev = torch.device("cuda:0")
-    if a.soft:
-        line = json.dumps(soft_mode(a, dev))
+    if a.soft or a.affine:
+        line = json.dumps((affine_mode if a.affine else soft_mode)(a, dev))
         print(line)
         if a.json:
             os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
