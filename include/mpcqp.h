@@ -581,6 +581,43 @@ int mpcqp_mpc_box_loop(int dtype, int batch, int nx, int nu, int N, int steps,
                        int32_t* status, int max_iter, double tol, void* stream);
 
 /*
+ * mpcqp_mpc_box_loop with a per-step linear term g_t in the gradient and a
+ * plant disturbance w_t, neither of which comes from the state: reference
+ * tracking with preview, a non-zero setpoint, a Monte-Carlo study of one
+ * controller under disturbances; H, F, A, Bm may still differ per instance.
+ * Per step
+ *   z_t = argmin 1/2 z'Hz + (F x_t + g_t)'z,  lb <= z <= ub
+ *   u_t = z_t[0..nu-1],  x_{t+1} = A x_t + B u_t + w_t
+ * It is the one-launch counterpart of T calls of mpcqp_gemv + mpcqp_solve_box
+ * with f = F x_t + g_t.  All arguments, limits, outputs, the status word and
+ * the defaults of max_iter and tol are those of mpcqp_mpc_box_loop.
+ * g: steps x batch x n (strideG = n), or steps x n shared by the batch
+ * (strideG = 0); time-major like the outputs.  w: steps x batch x nx.  Either
+ * may be NULL.  flags: 0 or MPCQP_LOOP_COLD (every step starts from the empty
+ * active set instead of the shifted previous one); any other bit is
+ * MPCQP_EINVAL.  With g = w = NULL and flags = 0 the call is exactly
+ * mpcqp_mpc_box_loop, bit for bit.  No scratch: each lane reads its own rows
+ * of g_t and w_t one step ahead, n + nx more elements per step and instance.
+ * The call only enqueues on `stream` and allocates nothing.
+ * Status: as mpcqp_mpc_box_loop; a non-finite entry of g_t gives NONFINITE at
+ * step t for that instance (and, as any failure, NaN in us, zs, x_{t+1} and
+ * the same code on its later steps); a non-finite w_t makes x_{t+1}
+ * non-finite: step t is reported as solved, step t+1 NONFINITE.  NONFINITE
+ * goes before INFEASIBLE before NOT_CONVEX; the other instances of the
+ * wavefront are not affected.
+ * Not supported: per-step bounds (lb/ub stay fixed), row shifts (the box loop
+ * has no rows), references for the bicycle controllers.
+ */
+int mpcqp_mpc_box_loop_affine(int dtype, int batch, int nx, int nu, int N, int steps, int flags,
+                              const void* H, int64_t strideH, const void* F, int64_t strideF,
+                              const void* A, int64_t strideA, const void* Bm, int64_t strideB,
+                              const void* x0, int64_t strideX0, const void* lb, int64_t strideLb,
+                              const void* ub, int64_t strideUb,
+                              const void* g, int64_t strideG, const void* w,
+                              void* xs, void* us, void* zs, int32_t* status, int max_iter,
+                              double tol, void* stream);
+
+/*
  * The receding-horizon loop of a linear MPC with row (state) constraints and
  * an input box, T steps in one launch: the MPC of sessions 2 and 3
  * (session_2/problem.py:4-33: double integrator, input box and the state box
@@ -688,9 +725,8 @@ int mpcqp_mpc_poly_loop_soft(int dtype, int batch, int n, int m, int nbox, int n
  * NONFINITE at step t for that instance (and, as any failure, on its later
  * steps); warm start, MPCQP_LOOP_COLD and the max_iter accounting are
  * unchanged.
- * Not supported: per-step input-box bounds (lbz/ubz stay fixed), g/e in
- * mpcqp_mpc_box_loop, a matrix-core product for -Hinv g, references for the
- * bicycle controllers.
+ * Not supported: per-step input-box bounds (lbz/ubz stay fixed), a
+ * matrix-core product for -Hinv g, references for the bicycle controllers.
  */
 size_t mpcqp_mpc_poly_loop_affine_workspace(int dtype, int batch, int n, int m, int nbox,
                                             int steps, int g_shared);

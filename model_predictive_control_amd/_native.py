@@ -21,7 +21,7 @@ TV = 1
 GAM_PACKED = 8  # mpcqp_condense: Gam as its lower block triangle
 IPM = 2
 STRICT = 4
-LOOP_COLD = 16  # mpcqp_mpc_poly_loop: every step from an empty active set
+LOOP_COLD = 16  # mpcqp_mpc_poly_loop, mpcqp_mpc_box_loop_affine: every step from an empty active set
 STATUS_POLISHED = 1 << 24
 STATUS_UNREFINED = 1 << 25
 STATUS_SOFTENED = 1 << 26  # mpcqp_mpc_poly_loop_soft: the step ends with a soft-active row
@@ -90,6 +90,8 @@ SIGNATURES = {
                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _i, _d, _vp,
                            ctypes.c_size_t, _vp]),
     "mpcqp_mpc_box_loop": (_i, [_i] * 6 + [_vp, _i64] * 7 + [_vp] * 3 + [_vp, _i, _d, _vp]),
+    "mpcqp_mpc_box_loop_affine": (_i, [_i] * 7 + [_vp, _i64] * 7 + [_vp, _i64, _vp] + [_vp] * 3 +
+                                  [_vp, _i, _d, _vp]),
     "mpcqp_mpc_poly_loop": (_i, [_i] * 9 + [_vp] * 5 + [_i64, _vp, _vp, _i64] + [_vp] * 8 +
                             [_i, _d, _vp]),
     "mpcqp_mpc_poly_loop_soft": (_i, [_i] * 9 + [_vp] * 5 + [_i64, _vp, _vp, _i64] + [_vp] * 11 +

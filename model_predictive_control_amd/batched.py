@@ -379,7 +379,8 @@ def mpc_ipm(A, B, Q, R, Qf, N: int, x0, xlo=None, xhi=None, lb=None, ub=None, c=
 
 def mpc_box_loop(A, B, Q, R, Qf, N: int, x0, lb=None, ub=None, steps: int = 1, *,
                  plans: bool = False, max_iter: int = 0, tol: float = 0.0,
-                 condensed: dict | None = None, out: dict | None = None) -> dict:
+                 condensed: dict | None = None, out: dict | None = None,
+                 g=None, w=None, x_ref=None, u_ref=None, cold: bool = False) -> dict:
     """The receding-horizon loop of the input-box MPC on a linear plant, on
     the device (include/mpcqp.h ``mpcqp_mpc_box_loop``): for t < steps,
     z_t = argmin 1/2 z'Hz + (F x_t)'z over lb <= z <= ub, x_{t+1} = A x_t + B
@@ -387,7 +388,16 @@ def mpc_box_loop(A, B, Q, R, Qf, N: int, x0, lb=None, ub=None, steps: int = 1, *
     policy of MPCController.solve (main.py:115-116).  A (nx,nx) | (b,nx,nx), B
     likewise; x0 (b, nx).  H and F come from ``condense`` of the same plant
     (once; pass ``condensed`` to reuse them).  Returns xs (steps+1, b, nx), us
-    (steps, b, nu), status (steps, b), and with ``plans`` zs (steps, b, N*nu)."""
+    (steps, b, nu), status (steps, b), and with ``plans`` zs (steps, b, N*nu).
+
+    ``g`` ((steps, n) shared by the batch, or (steps, b, n)) is a per-step
+    linear term: the step's gradient is F x_t + g_t.  ``x_ref`` / ``u_ref``
+    (shapes of ``tracking_terms``) build it from a reference trajectory
+    instead, for which the plant is condensed with Gam as well (per instance
+    when the plants are); passing both g and a reference is an error.  ``w``
+    (steps, b, nx) is a plant disturbance, x_{t+1} = A x_t + B u_t + w_t.
+    ``cold`` starts every step from the empty active set.  With any of these
+    the call goes to ``mpcqp_mpc_box_loop_affine``."""
     dt = A.dtype if isinstance(A, torch.Tensor) else torch.float64
     dev = A.device if isinstance(A, torch.Tensor) else torch.device("cuda")
     A, B = _dev(A, dt, dev), _dev(B, dt, dev)
@@ -396,7 +406,13 @@ def mpc_box_loop(A, B, Q, R, Qf, N: int, x0, lb=None, ub=None, steps: int = 1, *
     if x0.ndim != 2 or x0.shape[1] != nx:
         raise ValueError(f"x0 must be (batch, {nx}), got {tuple(x0.shape)}")
     batch, n, T = int(x0.shape[0]), N * nu, int(steps)
-    cd = condensed or condense(A, B, Q, R, Qf, N, outputs=("H", "F"))
+    tracking = x_ref is not None or u_ref is not None
+    if tracking and g is not None:
+        raise ValueError("mpc_box_loop: pass either g or a reference (x_ref / u_ref), not both")
+    cd = dict(condensed or condense(A, B, Q, R, Qf, N,
+                                    outputs=("H", "F", "Gam") if tracking else ("H", "F")))
+    if tracking and "Gam" not in cd:
+        cd["Gam"] = condense(A, B, Q, R, Qf, N, outputs=("Gam",))["Gam"]
     H, F = cd["H"], cd["F"]
     sH, _ = _inst(H, 1, "H")
     sF, _ = _inst(F, 2, "F")
@@ -408,6 +424,17 @@ def mpc_box_loop(A, B, Q, R, Qf, N: int, x0, lb=None, ub=None, steps: int = 1, *
     sB, _ = _inst(B, 2, "B")
     lbt, slb = _bound(lb, n, dt, dev)
     ubt, sub = _bound(ub, n, dt, dev)
+    if tracking:
+        Gam = cd["Gam"]
+        if Gam.ndim == 3 and Gam.shape[0] == 1:
+            Gam = Gam[0]
+        g = tracking_terms({"Gam": Gam}, _dev(Q, dt, dev), _weight_r(_dev(R, dt, dev), nu),
+                           _dev(Qf, dt, dev), N, T, x_ref, u_ref)
+    g, w = _dev(g, dt, dev), _dev(w, dt, dev)
+    if g is not None and tuple(g.shape) not in ((T, n), (T, batch, n)):
+        raise ValueError(f"g must be ({T}, {n}) or ({T}, {batch}, {n}), got {tuple(g.shape)}")
+    if w is not None and tuple(w.shape) != (T, batch, nx):
+        raise ValueError(f"w must be ({T}, {batch}, {nx}), got {tuple(w.shape)}")
     o = dict(out or {})
     shapes = dict(xs=((T + 1, batch, nx), dt), us=((T, batch, nu), dt),
                   status=((T, batch), torch.int32))
@@ -416,6 +443,15 @@ def mpc_box_loop(A, B, Q, R, Qf, N: int, x0, lb=None, ub=None, steps: int = 1, *
     for k, (shp, kd) in shapes.items():
         if k not in o:
             o[k] = torch.empty(shp, dtype=kd, device=dev)
+    if g is not None or w is not None or cold:
+        rc = _lib().mpcqp_mpc_box_loop_affine(
+            _code(dt), batch, nx, nu, N, T, nat.LOOP_COLD if cold else 0, _ptr(H), sH, _ptr(F), sF,
+            _ptr(A), sA, _ptr(B), sB, _ptr(x0), nx, _ptr(lbt), slb, _ptr(ubt), sub,
+            _ptr(g), 0 if g is None or g.ndim == 2 else n, _ptr(w),
+            _ptr(o["xs"]), _ptr(o["us"]), _ptr(o.get("zs")), _ptr(o["status"]), int(max_iter),
+            float(tol), _stream())
+        nat.check(rc, "mpcqp_mpc_box_loop_affine")
+        return o
     rc = _lib().mpcqp_mpc_box_loop(_code(dt), batch, nx, nu, N, T, _ptr(H), sH, _ptr(F), sF,
                                    _ptr(A), sA, _ptr(B), sB, _ptr(x0), nx, _ptr(lbt), slb,
                                    _ptr(ubt), sub, _ptr(o["xs"]), _ptr(o["us"]), _ptr(o.get("zs")),
@@ -736,17 +772,20 @@ def tracking_terms(cd, Q, R, Qf, N: int, T: int, x_ref=None, u_ref=None):
     """The per-step linear term g of ``PolyQP.loop`` for the tracking cost
     sum_k (x_k - r_{t+k})'Q(x_k - r_{t+k}) + (u_k - ubar_{t+k})'R(u_k - ubar_{t+k})
     (terminal weight Qf) of an MPC condensed as ``cd`` (a dict with Gam, (N*nx,
-    N*nu)):  g_t = -Gam' Qhat rbar_t - Rhat ubar_t  with Qhat = blkdiag(Q, ..,
+    N*nu), or (b, N*nx, N*nu) from per-instance plants):  g_t = -Gam' Qhat rbar_t - Rhat ubar_t  with Qhat = blkdiag(Q, ..,
     Q, Qf), Rhat = blkdiag(R, .., R), rbar_t = x_ref[t+1 : t+N+1], ubar_t =
     u_ref[t : t+N], both references indexed by absolute time: x_ref (nx,)
     (a setpoint), (T+N+1, nx) or (b, T+N+1, nx); u_ref (nu,), (T+N, nu) or (b,
-    T+N, nu).  Returns g (T, n), or (T, b, n) when a reference is per instance.
-    Plain tensor algebra on the device of ``cd`` (CPU tensors work too)."""
+    T+N, nu).  Returns g (T, n), or (T, b, n) when a reference or Gam is per
+    instance.  Plain tensor algebra on the device of ``cd`` (CPU tensors work
+    too)."""
     Gam = cd["Gam"]
+    if Gam.ndim not in (2, 3):
+        raise ValueError(f"Gam must be (N*nx, n) or (b, N*nx, n), got {tuple(Gam.shape)}")
     dt, dev = Gam.dtype, Gam.device
     N, T = int(N), int(T)
-    n = int(Gam.shape[1])
-    nx, nu = int(Gam.shape[0]) // N, n // N
+    n = int(Gam.shape[-1])
+    nx, nu = int(Gam.shape[-2]) // N, n // N
     as_t = lambda v: torch.as_tensor(v, dtype=dt, device=dev)  # noqa: E731
     if x_ref is None and u_ref is None:
         raise ValueError("tracking_terms needs x_ref or u_ref")
@@ -775,6 +814,14 @@ def tracking_terms(cd, Q, R, Qf, N: int, T: int, x_ref=None, u_ref=None):
         parts = [v if v.ndim == 3 else v.expand(b, *v.shape) for v in parts]
     if len(parts) == 2 and parts[0].shape[:-1] != parts[1].shape[:-1]:
         raise ValueError("x_ref and u_ref have different batch sizes")
+    if Gam.ndim == 3:
+        # per-instance plants: the state part is a batched product, (b, T, n)
+        if parts[0].ndim == 3 and parts[0].shape[0] != Gam.shape[0]:
+            raise ValueError(f"the references have batch {parts[0].shape[0]}, Gam {Gam.shape[0]}")
+        g = torch.zeros((Gam.shape[0], T, n), dtype=dt, device=dev)
+        for v, mat in zip(parts, mats):
+            g = g - v @ mat
+        return g.transpose(0, 1).contiguous()
     g = -(torch.cat(parts, dim=-1) @ torch.cat(mats, dim=0))
     return g.transpose(0, 1).contiguous() if g.ndim == 3 else g.contiguous()
 

@@ -185,22 +185,36 @@ class ClosedLoop:
         s["sqp"].reset()
 
 
-def lti_box_mpc_loop(A, B, Q, R, Qf, N: int, X0, lb, ub, steps: int) -> dict:
+def lti_box_mpc_loop(A, B, Q, R, Qf, N: int, X0, lb, ub, steps: int, *, x_ref=None, u_ref=None,
+                     w=None) -> dict:
     """The receding-horizon loop of the input-box MPC on a linear plant
     (LinearSystem.simulate, session_1/LinearSystem.py:20-26, with the
     box-constrained MPC step as the policy; simulate(...) main.py:270-271),
     all ``steps`` in one launch (``batched.mpc_box_loop``; each step
     warm-started from the shifted previous active set).  X0 (b, nx) ->
     xs (T+1, b, nx), us (T, b, nu), success (T, b), iters (T, b), and the
-    ControllerLog input_prediction (T, b, N, nu)."""
+    ControllerLog input_prediction (T, b, N, nu).
+    ``x_ref`` ((nx,), (T+N+1, nx) or (b, T+N+1, nx)) and ``u_ref`` ((nu,),
+    (T+N, nu) or (b, T+N, nu)), indexed by absolute time, make the cost track a
+    reference with preview (``batched.tracking_terms``); with ``x_ref`` the
+    result has tracking_error (T, b, nx) = xs[1:] - x_ref[1:T+1].  ``w`` (T, b,
+    nx) is a plant disturbance."""
     dev = torch.device("cuda")
-    t = lambda a: torch.as_tensor(a, dtype=torch.float64, device=dev)  # noqa: E731
+    t = lambda a: None if a is None else torch.as_tensor(a, dtype=torch.float64, device=dev)  # noqa: E731
     A, B, X0 = t(A), t(B), t(X0).reshape(-1, t(A).shape[-1])
-    r = batched.mpc_box_loop(A, B, t(Q), t(R), t(Qf), N, X0, lb, ub, steps, plans=True)
+    T = int(steps)
+    r = batched.mpc_box_loop(A, B, t(Q), t(R), t(Qf), N, X0, lb, ub, T, plans=True,
+                             x_ref=t(x_ref), u_ref=t(u_ref), w=t(w))
     nu = B.shape[-1]
-    return {"xs": r["xs"], "us": r["us"], "success": batched.status_code(r["status"]) == 0,
-            "iters": batched.status_iters(r["status"]),
-            "input_prediction": r["zs"].reshape(steps, X0.shape[0], N, nu)}
+    out = {"xs": r["xs"], "us": r["us"], "success": batched.status_code(r["status"]) == 0,
+           "iters": batched.status_iters(r["status"]),
+           "input_prediction": r["zs"].reshape(steps, X0.shape[0], N, nu)}
+    if x_ref is not None:
+        xr = t(x_ref)
+        xr = xr[..., 1:T + 1, :] if xr.ndim > 1 else xr
+        out["tracking_error"] = r["xs"][1:] - (xr.transpose(0, 1) if xr.ndim == 3 else
+                                               xr.unsqueeze(1) if xr.ndim == 2 else xr)
+    return out
 
 
 def lti_mpc_loop(problem, X0, steps: int, *, N: int | None = None, Qf=None, plant=None, w=None,

@@ -22,6 +22,19 @@
 // and the Goldfarb-Idnani iterations only correct the guess (gi_box_st).  No
 // Riccati, no -H^-1, no HBM traffic per step but x, u, the status and the
 // (optional) input plan.
+//
+// mpcqp_mpc_box_loop_affine is the AFFINE instantiation: a per-step linear term
+// g_t in the gradient (f_t = F x_t + g_t: reference tracking, batched.
+// tracking_terms) and a plant disturbance w_t (x_{t+1} = A x_t + B u_0 + w_t),
+// both read from HBM by the lane that owns the row (rows q and q + 16 of f,
+// row q of x) one step ahead: g_{t+1} is loaded as soon as step t's f is in
+// LDS and first used at the top of step t + 1, w_{t+1} as soon as w_t has gone
+// into x_{t+1} and first used at the end of step t + 1, so their latency lies
+// under the active set and each value needs one register, the one its
+// predecessor has just left.  MPCQP_LOOP_COLD (a runtime argument of the same
+// instantiation) starts every step from the empty set.
+#include <type_traits>
+
 #include "quad.hpp"
 #include "quad_api.hpp"
 
@@ -44,6 +57,19 @@ struct LoopArgs {
   int max_iter;
   T tol;
 };
+
+// The AFFINE instantiation's arguments: g_t of instance b at g + t * gT + b * sG
+// (sG = 0, gT = n: shared by the batch; sG = n, gT = batch * n: per instance),
+// w_t at w + (t * batch + b) * nx; either may be null.
+template <typename T>
+struct LoopAffineArgs : LoopArgs<T> {
+  const T* g; int64_t sG, gT;
+  const T* w;
+  int cold;
+};
+
+template <typename T, bool AFFINE>
+using LoopArgsOf = std::conditional_t<AFFINE, LoopAffineArgs<T>, LoopArgs<T>>;
 
 template <typename T, int NX, int NU, int BS>
 struct LoopLds {
@@ -68,14 +94,46 @@ struct LoopOcc {
   static constexpr int w = BS <= 2 ? 4 : 1;
 };
 
-template <typename T, int NX, int NU, int BS>
-__global__ __launch_bounds__(64, (LoopOcc<T, BS>::w)) void box_loop_kernel(LoopArgs<T> a) {
+// A wave-uniform pointer to global memory, held in scalar registers.
+template <typename T>
+using GlobalPtr = const __attribute__((address_space(1))) T*;
+template <typename T>
+__device__ __forceinline__ GlobalPtr<T> sbase(const T* p) {
+  const unsigned long long v = (unsigned long long)p;
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(v & 0xffffffffull));
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32));
+  return (GlobalPtr<T>)(((unsigned long long)hi << 32) | lo);
+}
+
+// The element `bytes` (a 32-bit per-lane offset) behind a scalar base: the
+// address form global loads take without a per-lane 64-bit pointer.
+template <typename T>
+__device__ __forceinline__ T at_bytes(GlobalPtr<T> base, unsigned bytes) {
+  return *(GlobalPtr<T>)((const __attribute__((address_space(1))) char*)base + bytes);
+}
+
+// The same address form for a store: base[row + off] with a wave-uniform row
+// (64-bit, scalar) and a small per-lane off, formed at the store.
+template <typename T>
+__device__ __forceinline__ void put_at(T* base, int64_t row, unsigned off, T v) {
+  const unsigned long long p = (unsigned long long)(base + row);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(p & 0xffffffffull));
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(p >> 32));
+  asm volatile("" : "+v"(off));
+  *(__attribute__((address_space(1))) T*)((__attribute__((address_space(1))) char*)(
+        ((unsigned long long)hi << 32) | lo) + off * (unsigned)sizeof(T)) = v;
+}
+
+template <typename T, int NX, int NU, int BS, bool AFFINE = false>
+__global__ __launch_bounds__(64, (LoopOcc<T, BS>::w)) void box_loop_kernel(
+    LoopArgsOf<T, AFFINE> a) {
   using Lq = LoopLds<T, NX, NU, BS>;
   using Box = QBoxLds<T, BS>;
   constexpr int NMAX = Lq::NMAX;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const int lane = threadIdx.x, g = lane >> 4, q = lane & 15;
   const int b = blockIdx.x * 4 + g;
+  [[maybe_unused]] const int64_t b0 = (int64_t)blockIdx.x * 4;  // the wave's first instance
   const bool live = b < a.batch;
   const int bl = live ? b : 0;
   const int n = a.n, nx = a.nx, nu = a.nu, P = n * (n + 1) / 2;
@@ -150,9 +208,53 @@ __global__ __launch_bounds__(64, (LoopOcc<T, BS>::w)) void box_loop_kernel(LoopA
     okst[r] = (lbs[i] > -Lim<T>::inf() ? 1 : 0) | (ubs[i] < Lim<T>::inf() ? 2 : 0);
   }
 
+  // AFFINE: this lane's entries of g (rows q and, where NMAX > 16, q + 16 of f)
+  // and of w (row q of x), loaded one step ahead into the register that the
+  // step before has just left; 0 where there is none.  Where four waves share
+  // a SIMD (BS <= 2: n <= 8, 128 VGPRs) lanes 8.. of the group have no row of
+  // g, and w_t[j] travels in lane 8 + j of g's register (WPACK): the loads are
+  // per lane, so the two halves of the register are reloaded at different
+  // points of the step.  The address is a wave-uniform base of the step (in
+  // scalar registers: sbase) plus a small per-lane offset, so that no per-lane
+  // pointer lives across the step.
+  constexpr bool WPACK = BS <= 2;
+  [[maybe_unused]] T gn0 = T(0), gn1 = T(0), wn = T(0);
+  [[maybe_unused]] auto fetch_g = [&](int t) {
+    if constexpr (AFFINE) {
+      if (live && a.g) {
+        const auto gt = sbase(a.g + (int64_t)t * a.gT + b0 * a.sG);
+        unsigned o = a.sG ? (unsigned)(g * n + q) : (unsigned)q;
+        asm volatile("" : "+v"(o));  // formed here, every step: nothing of it kept in the loop
+        if (q < n) gn0 = at_bytes(gt, o * (unsigned)sizeof(T));
+        if constexpr (NMAX > 16)
+          if (q + 16 < n) gn1 = at_bytes(gt, (o + 16u) * (unsigned)sizeof(T));
+      }
+    }
+  };
+  [[maybe_unused]] auto fetch_w = [&](int t) {
+    if constexpr (AFFINE) {
+      const int j = WPACK ? q - 8 : q;
+      if (live && a.w && j >= 0 && j < nx) {
+        const auto wt = sbase(a.w + ((int64_t)t * a.batch + b0) * nx);
+        unsigned o = (unsigned)(g * nx + j);
+        asm volatile("" : "+v"(o));
+        (WPACK ? gn0 : wn) = at_bytes(wt, o * (unsigned)sizeof(T));
+      }
+    }
+  };
+  if constexpr (AFFINE)
+    if (a.steps > 0) {
+      fetch_g(0);
+      fetch_w(0);
+    }
+
   for (int t = 0; t < a.steps; ++t) {
     // record x_t; f = F x_t (rows q, q + 16 of the group)
-    if (live && q < nx) a.xs[((int64_t)t * a.batch + b) * nx + q] = xg[q];
+    if constexpr (AFFINE) {  // (the stores by put_at: no per-lane pointers kept in the loop)
+      if (live && q < nx) put_at(a.xs, ((int64_t)t * a.batch + b0) * nx, (unsigned)(g * nx + q), xg[q]);
+    } else {
+      if (live && q < nx) a.xs[((int64_t)t * a.batch + b) * nx + q] = xg[q];
+    }
     // A NaN/Inf in x_t (from x0, A, B or a failed step; H and F are checked at
     // stage-in) makes f non-finite: every violation is then NaN, the group
     // "settles" and the final clamp turns the NaN z into a bound.  Every lane
@@ -160,13 +262,26 @@ __global__ __launch_bounds__(64, (LoopOcc<T, BS>::w)) void box_loop_kernel(LoopA
     bool nfx = false;
 #pragma unroll
     for (int j = 0; j < NX; ++j) nfx |= !finite(xg[j]);
+    if constexpr (AFFINE) {
+#ifdef MPCQP_BOX_LOOP_PLAIN_LOAD  // A/B variant: load g_t where it is used
+      if (t > 0) fetch_g(t);
+#endif
+      // a non-finite g_t fails this group alone (its own ballot bits)
+      nfx |= (__ballot((!finite(gn0) && !(WPACK && q >= 8)) || !finite(gn1)) & gmask) != 0;
+    }
     for (int i = q; i < NMAX; i += 16) {
       T s = T(0);
 #pragma unroll
       for (int j = 0; j < NX; ++j) s = fma(Fs[i * NX + j], xg[j], s);
+      if constexpr (AFFINE) s += i < 16 ? gn0 : gn1;
       fs[i] = s;
     }
     lds_exchange();
+#ifndef MPCQP_BOX_LOOP_PLAIN_LOAD
+    // g_{t+1}: in flight during the active set below; never past the last row
+    if constexpr (AFFINE)
+      if (t + 1 < a.steps) fetch_g(t + 1);
+#endif
     bool nf = false;
     M.load_packed(Ps, n, nf);
     // sweep H on the free rows of the warm-start set: free-row mask of the
@@ -219,13 +334,26 @@ __global__ __launch_bounds__(64, (LoopOcc<T, BS>::w)) void box_loop_kernel(LoopA
         const int i = M.bi * BS + r;
         if (i < NU) ug[i] = zr[r];
         if (i < NMAX) sg[i] = (T)st[r];
-        if (live && a.zs && i < n) a.zs[((int64_t)t * a.batch + b) * n + i] = zr[r];
+        if constexpr (AFFINE) {
+          if (live && a.zs && i < n)
+            put_at(a.zs, ((int64_t)t * a.batch + b0) * n, (unsigned)(g * n + i), zr[r]);
+        } else {
+          if (live && a.zs && i < n) a.zs[((int64_t)t * a.batch + b) * n + i] = zr[r];
+        }
       }
     }
-    if (live && q == 0)
-      a.status[(int64_t)t * a.batch + b] = (code & 0xff) | (((iters + sweeps) & 0xffff) << 8);
+    const int word = (code & 0xff) | (((iters + sweeps) & 0xffff) << 8);
+    if constexpr (AFFINE) {
+      if (live && q == 0) put_at(a.status, (int64_t)t * a.batch + b0, (unsigned)g, (int32_t)word);
+    } else {
+      if (live && q == 0) a.status[(int64_t)t * a.batch + b] = word;
+    }
     lds_exchange();
-    if (live && q < nu) a.us[((int64_t)t * a.batch + b) * nu + q] = ug[q];
+    if constexpr (AFFINE) {
+      if (live && q < nu) put_at(a.us, ((int64_t)t * a.batch + b0) * nu, (unsigned)(g * nu + q), ug[q]);
+    } else {
+      if (live && q < nu) a.us[((int64_t)t * a.batch + b) * nu + q] = ug[q];
+    }
     // plant: x_{t+1} = A x_t + B u_0
     T xn = T(0);
     if (q < NX) {
@@ -234,6 +362,16 @@ __global__ __launch_bounds__(64, (LoopOcc<T, BS>::w)) void box_loop_kernel(LoopA
 #pragma unroll
       for (int j = 0; j < NU; ++j) xn = fma(Bs[q * NU + j], ug[j], xn);
     }
+#ifdef MPCQP_BOX_LOOP_PLAIN_LOAD
+    if constexpr (AFFINE)
+      if (t > 0) fetch_w(t);
+#endif
+    if constexpr (AFFINE) xn += WPACK ? dpp<0x128>(gn0) : wn;  // row_ror:8 = lane ^ 8
+#ifndef MPCQP_BOX_LOOP_PLAIN_LOAD
+    // w_{t+1}, first used a whole step from here
+    if constexpr (AFFINE)
+      if (t + 1 < a.steps) fetch_w(t + 1);
+#endif
     // warm start of the next step: row i takes row i + nu's state (the last
     // stage keeps its own); a failed step restarts cold
 #pragma unroll
@@ -241,73 +379,80 @@ __global__ __launch_bounds__(64, (LoopOcc<T, BS>::w)) void box_loop_kernel(LoopA
       const int i = M.bi * BS + r;
       const int src = i + nu < n ? i + nu : i;
       const int s = okc ? ((int)sg[src] & okst[r]) : 0;  // states are 0, 1, 2
-      st[r] = i < n ? s : 3;
+      if constexpr (AFFINE)
+        st[r] = i < n && !a.cold ? s : (i < n ? 0 : 3);
+      else
+        st[r] = i < n ? s : 3;
     }
     lds_exchange();
     if (q < NX) xg[q] = xn;
     lds_exchange();
   }
-  if (live && q < nx) a.xs[((int64_t)a.steps * a.batch + b) * nx + q] = xg[q];
+  if constexpr (AFFINE) {
+    if (live && q < nx)
+      put_at(a.xs, ((int64_t)a.steps * a.batch + b0) * nx, (unsigned)(g * nx + q), xg[q]);
+  } else {
+    if (live && q < nx) a.xs[((int64_t)a.steps * a.batch + b) * nx + q] = xg[q];
+  }
 }
 
-template <typename T, int NX, int NU, int BS>
-static int launch_loop(const LoopArgs<T>& a, hipStream_t st) {
+template <typename T, int NX, int NU, int BS, bool AFFINE>
+static int launch_loop(const LoopArgsOf<T, AFFINE>& a, hipStream_t st) {
   using Lq = LoopLds<T, NX, NU, BS>;
   const size_t bytes = (size_t)4 * Lq::size * sizeof(T);
   if (bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)box_loop_kernel<T, NX, NU, BS>,
+    hipError_t e = hipFuncSetAttribute((const void*)box_loop_kernel<T, NX, NU, BS, AFFINE>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(box_loop)");
   }
-  hipLaunchKernelGGL((box_loop_kernel<T, NX, NU, BS>), dim3((unsigned)((a.batch + 3) / 4)),
-                     dim3(64), bytes, st, a);
+  hipLaunchKernelGGL((box_loop_kernel<T, NX, NU, BS, AFFINE>),
+                     dim3((unsigned)((a.batch + 3) / 4)), dim3(64), bytes, st, a);
   MPCQP_CHECK_LAUNCH("box_loop_kernel");
   return MPCQP_OK;
 }
 
-template <typename T, int NX, int NU>
-static int loop_bs(const LoopArgs<T>& a, hipStream_t st) {
+template <typename T, int NX, int NU, bool AFFINE>
+static int loop_bs(const LoopArgsOf<T, AFFINE>& a, hipStream_t st) {
   switch ((a.n + 3) / 4) {
-    case 1: return launch_loop<T, NX, NU, 1>(a, st);
-    case 2: return launch_loop<T, NX, NU, 2>(a, st);
-    case 3: return launch_loop<T, NX, NU, 3>(a, st);
-    case 4: return launch_loop<T, NX, NU, 4>(a, st);
-    case 5: return launch_loop<T, NX, NU, 5>(a, st);
-    case 6: return launch_loop<T, NX, NU, 6>(a, st);
-    case 7: return launch_loop<T, NX, NU, 7>(a, st);
-    default: return launch_loop<T, NX, NU, 8>(a, st);
+    case 1: return launch_loop<T, NX, NU, 1, AFFINE>(a, st);
+    case 2: return launch_loop<T, NX, NU, 2, AFFINE>(a, st);
+    case 3: return launch_loop<T, NX, NU, 3, AFFINE>(a, st);
+    case 4: return launch_loop<T, NX, NU, 4, AFFINE>(a, st);
+    case 5: return launch_loop<T, NX, NU, 5, AFFINE>(a, st);
+    case 6: return launch_loop<T, NX, NU, 6, AFFINE>(a, st);
+    case 7: return launch_loop<T, NX, NU, 7, AFFINE>(a, st);
+    default: return launch_loop<T, NX, NU, 8, AFFINE>(a, st);
   }
 }
 
-template <typename T>
-static int loop_t(const LoopArgs<T>& a, hipStream_t st) {
-  if (a.nx <= 2 && a.nu <= 1) return loop_bs<T, 2, 1>(a, st);
-  if (a.nx <= 2 && a.nu <= 2) return loop_bs<T, 2, 2>(a, st);
-  return loop_bs<T, 4, 2>(a, st);
+template <typename T, bool AFFINE>
+static int loop_t(const LoopArgsOf<T, AFFINE>& a, hipStream_t st) {
+  if (a.nx <= 2 && a.nu <= 1) return loop_bs<T, 2, 1, AFFINE>(a, st);
+  if (a.nx <= 2 && a.nu <= 2) return loop_bs<T, 2, 2, AFFINE>(a, st);
+  return loop_bs<T, 4, 2, AFFINE>(a, st);
 }
 
-}  // namespace mpcqp
-
-extern "C" int mpcqp_mpc_box_loop(int dtype, int batch, int nx, int nu, int N, int steps,
-                                  const void* H, int64_t strideH, const void* F, int64_t strideF,
-                                  const void* A, int64_t strideA, const void* Bm, int64_t strideB,
-                                  const void* x0, int64_t strideX0, const void* lb,
-                                  int64_t strideLb, const void* ub, int64_t strideUb, void* xs,
-                                  void* us, void* zs, int32_t* status, int max_iter, double tol,
-                                  void* stream) {
-  using namespace mpcqp;
-  MPCQP_CHECK_ARG(dtype == MPCQP_F64 || dtype == MPCQP_F32, "mpcqp_mpc_box_loop: bad dtype %d",
-                  dtype);
-  MPCQP_CHECK_ARG(batch >= 0 && N >= 1 && steps >= 0, "mpcqp_mpc_box_loop: bad sizes");
+// Both entry points: g == w == nullptr and flags == 0 launch the kernels of
+// mpcqp_mpc_box_loop.
+static int box_loop_entry(const char* who, int dtype, int batch, int nx, int nu, int N, int steps,
+                          int flags, const void* H, int64_t strideH, const void* F,
+                          int64_t strideF, const void* A, int64_t strideA, const void* Bm,
+                          int64_t strideB, const void* x0, int64_t strideX0, const void* lb,
+                          int64_t strideLb, const void* ub, int64_t strideUb, const void* g,
+                          int64_t strideG, const void* w, void* xs, void* us, void* zs,
+                          int32_t* status, int max_iter, double tol, void* stream) {
+  MPCQP_CHECK_ARG(dtype == MPCQP_F64 || dtype == MPCQP_F32, "%s: bad dtype %d", who, dtype);
+  MPCQP_CHECK_ARG(batch >= 0 && N >= 1 && steps >= 0, "%s: bad sizes", who);
   MPCQP_CHECK_ARG(nx >= 1 && nx <= 4 && nu >= 1 && nu <= 2 && N * nu <= 32,
-                  "mpcqp_mpc_box_loop: nx=%d nu=%d N=%d outside nx <= 4, nu <= 2, N*nu <= 32",
-                  nx, nu, N);
+                  "%s: nx=%d nu=%d N=%d outside nx <= 4, nu <= 2, N*nu <= 32", who, nx, nu, N);
+  MPCQP_CHECK_ARG((flags & ~MPCQP_LOOP_COLD) == 0, "%s: unknown flags 0x%x", who, flags);
   MPCQP_CHECK_ARG(H && F && A && Bm && x0 && xs && (steps == 0 || (us && status)),
-                  "mpcqp_mpc_box_loop: H, F, A, B, x0, xs (and us, status for steps > 0) "
-                  "are required");
+                  "%s: H, F, A, B, x0, xs (and us, status for steps > 0) are required", who);
   MPCQP_CHECK_ARG(strideH >= 0 && strideF >= 0 && strideA >= 0 && strideB >= 0 &&
                       strideX0 >= 0 && strideLb >= 0 && strideUb >= 0,
-                  "mpcqp_mpc_box_loop: negative stride");
+                  "%s: negative stride", who);
+  MPCQP_CHECK_ARG(!g || strideG == 0 || strideG == N * nu,
+                  "%s: strideG=%lld is neither 0 nor n=%d", who, (long long)strideG, N * nu);
   if (batch == 0) return MPCQP_OK;
   auto fill = [&](auto& a, auto tp) {
     using T = decltype(tp);
@@ -320,13 +465,51 @@ extern "C" int mpcqp_mpc_box_loop(int dtype, int batch, int nx, int nu, int N, i
     a.max_iter = max_iter > 0 ? max_iter : 3 * N * nu + 30;
     a.tol = tol > 0 ? (T)tol : (dtype == MPCQP_F64 ? (T)1e-12 : (T)1e-6);
   };
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == MPCQP_F64) {
-    LoopArgs<double> a;
-    fill(a, 0.0);
-    return loop_t(a, st);
-  }
-  LoopArgs<float> a;
-  fill(a, 0.0f);
-  return loop_t(a, st);
+  auto run = [&](auto tp) {
+    using T = decltype(tp);
+    hipStream_t st = (hipStream_t)stream;
+    if (g || w || flags) {
+      LoopAffineArgs<T> a;
+      fill(a, tp);
+      a.g = (const T*)g; a.sG = strideG;
+      a.gT = strideG == 0 ? (int64_t)N * nu : (int64_t)batch * N * nu;
+      a.w = (const T*)w;
+      a.cold = (flags & MPCQP_LOOP_COLD) ? 1 : 0;
+      return loop_t<T, true>(a, st);
+    }
+    LoopArgs<T> a;
+    fill(a, tp);
+    return loop_t<T, false>(a, st);
+  };
+  return dtype == MPCQP_F64 ? run(0.0) : run(0.0f);
+}
+
+}  // namespace mpcqp
+
+extern "C" int mpcqp_mpc_box_loop(int dtype, int batch, int nx, int nu, int N, int steps,
+                                  const void* H, int64_t strideH, const void* F, int64_t strideF,
+                                  const void* A, int64_t strideA, const void* Bm, int64_t strideB,
+                                  const void* x0, int64_t strideX0, const void* lb,
+                                  int64_t strideLb, const void* ub, int64_t strideUb, void* xs,
+                                  void* us, void* zs, int32_t* status, int max_iter, double tol,
+                                  void* stream) {
+  return mpcqp::box_loop_entry("mpcqp_mpc_box_loop", dtype, batch, nx, nu, N, steps, 0, H, strideH,
+                               F, strideF, A, strideA, Bm, strideB, x0, strideX0, lb, strideLb, ub,
+                               strideUb, nullptr, 0, nullptr, xs, us, zs, status, max_iter, tol,
+                               stream);
+}
+
+extern "C" int mpcqp_mpc_box_loop_affine(int dtype, int batch, int nx, int nu, int N, int steps,
+                                         int flags, const void* H, int64_t strideH, const void* F,
+                                         int64_t strideF, const void* A, int64_t strideA,
+                                         const void* Bm, int64_t strideB, const void* x0,
+                                         int64_t strideX0, const void* lb, int64_t strideLb,
+                                         const void* ub, int64_t strideUb, const void* g,
+                                         int64_t strideG, const void* w, void* xs, void* us,
+                                         void* zs, int32_t* status, int max_iter, double tol,
+                                         void* stream) {
+  return mpcqp::box_loop_entry("mpcqp_mpc_box_loop_affine", dtype, batch, nx, nu, N, steps, flags,
+                               H, strideH, F, strideF, A, strideA, Bm, strideB, x0, strideX0, lb,
+                               strideLb, ub, strideUb, g, strideG, w, xs, us, zs, status, max_iter,
+                               tol, stream);
 }
