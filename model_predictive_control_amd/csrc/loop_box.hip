@@ -94,6 +94,15 @@ struct LoopOcc {
   static constexpr int w = BS <= 2 ? 4 : 1;
 };
 
+// Keyed reductions (Key, quad.hpp) per instantiation.  The affine fp64 NX = 4
+// NU = 2 BS = 5 kernel sits at 256 VGPRs and would take one AGPR more (257: the
+// bound of its registers 2 -> 1 waves): it keeps the compare-and-select
+// reductions.
+template <typename T, int NX, int NU, int BS, bool AFFINE>
+struct LoopKeyed {
+  static constexpr bool v = !(sizeof(T) == 8 && NX == 4 && NU == 2 && BS == 5 && AFFINE);
+};
+
 // A wave-uniform pointer to global memory, held in scalar registers.
 template <typename T>
 using GlobalPtr = const __attribute__((address_space(1))) T*;
@@ -317,7 +326,8 @@ __global__ __launch_bounds__(64, (LoopOcc<T, BS>::w)) void box_loop_kernel(
     if (code == MPCQP_STATUS_OPTIMAL && !okp) code = MPCQP_STATUS_NOT_CONVEX;
     T zr[BS];
     int iters = 0;
-    const int c2 = gi_box_st<T, BS, true>(M, gb, fs, lbs, ubs, n, a.max_iter, a.tol,
+    using Own = RowOwn<QSym<T, BS>, QRowOwned<QSym<T, BS>>::v, LoopKeyed<T, NX, NU, BS, AFFINE>::v>;
+    const int c2 = gi_box_st<T, BS, true, QSym<T, BS>, Own>(M, gb, fs, lbs, ubs, n, a.max_iter, a.tol,
                                           live && code == MPCQP_STATUS_OPTIMAL, zr, iters, st
                                           MPCQP_CLK_ARG);
     if (code == MPCQP_STATUS_OPTIMAL) code = c2;

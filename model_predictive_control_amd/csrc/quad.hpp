@@ -238,8 +238,27 @@ struct QSym {
   }
 };
 
-// Per-group LDS block for the box active set: [Mat::BUF | f | lb | ub], the
-// vectors indexed by (padded) row.
+// Keyed reductions (below, next to dpp_argmax): which layouts reduce the scan,
+// the ratio test and the warm-start release scan on one fp64 key instead of
+// a (value, index, payload) triple.  fp64 only: in fp32 the index bits would
+// make values within 2^-18 relative compare equal.
+// MPCQP_KEYED_REDUCE=0 builds the compare-and-select reductions everywhere (A/B).
+#ifndef MPCQP_KEYED_REDUCE
+#define MPCQP_KEYED_REDUCE 1
+#endif
+template <class Mat>
+struct QKeyed {
+  static constexpr bool v = false;
+};
+template <int BS>
+struct QKeyed<QSym<double, BS>> {
+  static constexpr bool v = MPCQP_KEYED_REDUCE != 0;
+};
+
+// Per-group LDS block for the box active set: [Mat::BUF | f | lb | ub | z],
+// the vectors indexed by (padded) row; oBuf = 0, so the tile pointer gb is
+// the block's base.  z (keyed layouts only, otherwise empty) is the owners'
+// copy of the primal iterate, from which a new pivot reads z_p.
 template <class Mat>
 struct GBoxLds {
   static constexpr int NMAX = Mat::NMAX;
@@ -248,7 +267,8 @@ struct GBoxLds {
   static constexpr int oF = Mat::BUF;
   static constexpr int oLb = oF + NV;
   static constexpr int oUb = oLb + NV;
-  static constexpr int size = oUb + NV;
+  static constexpr int oZ = oUb + NV;
+  static constexpr int size = oZ + (QKeyed<Mat>::v ? NV : 0);
 };
 template <typename T, int BS>
 using QBoxLds = GBoxLds<QSym<T, BS>>;
@@ -331,6 +351,79 @@ __device__ __forceinline__ X quad_lane(X v) {
   return dpp<J | (J << 2) | (J << 4) | (J << 6)>(v);
 }
 
+// Keyed reductions.  The order of the arg-reductions above (value, then the
+// smaller index) fits in one fp64 key: the low KB = ceil(log2 NMAX) mantissa
+// bits of the value are replaced by a code of the row index, and a reduction
+// step is two DPP moves and one v_max_f64 / v_min_f64 instead of the moves,
+// compares and selects of a (value, index, payload) triple.
+//   arg-max of positive values   code = 2^KB-1-idx  (larger key = smaller index)
+//   arg-min of non-negative ones code = idx
+//   arg-min of negative ones     code = 2^KB-1-idx  (the magnitude grows with the code)
+// Values that are exactly equal resolve to the smaller index, as before;
+// values that differ only in the low KB bits (2^-47 relative at KB = 5) now
+// compare equal and resolve to the smaller index too.  A key must be finite
+// (index bits in an infinity make a NaN): non-candidates and infinite or NaN
+// values map to -/+ big(), the largest finite value with its low bits clear,
+// before packing; with any code a sentinel still orders below (above) every
+// candidate.  The value that comes out of a reduction has its low bits clear.
+constexpr int key_bits(int nmax) {
+  int b = 0;
+  while ((1 << b) < nmax) ++b;
+  return b;
+}
+template <int KB>
+struct Key {
+  static constexpr long long MASK = (1ll << KB) - 1;
+  static __device__ __forceinline__ double clear(double v) {
+    return __longlong_as_double(__double_as_longlong(v) & ~MASK);
+  }
+  static __device__ __forceinline__ double pack(double v, int code) {
+    return __longlong_as_double((__double_as_longlong(v) & ~MASK) | (long long)(unsigned)code);
+  }
+  static __device__ __forceinline__ int code(double key) {
+    return (int)(__double_as_longlong(key) & MASK);
+  }
+  static __device__ __forceinline__ double big() {
+    return __longlong_as_double(0x7fefffffffffffffll & ~MASK);
+  }
+};
+// Max / min of two keys.  A key comes out of integer operations and DPP moves,
+// so the compiler cannot know that it is no signalling NaN and puts a
+// canonicalising v_max_f64 x, x in front of every fmax / fmin of one: one more
+// dependent fp64 instruction per reduction step.  Keys are finite by
+// construction, so the bare instruction is the same function of them.
+// MPCQP_KEY_BARE=0 builds fmax / fmin (A/B: config 2, 0.04487 -> 0.04425 ms per
+// step, ranges 0.04480-0.04496 and 0.04417-0.04427, results bit-identical).
+#ifndef MPCQP_KEY_BARE
+#define MPCQP_KEY_BARE 1
+#endif
+__device__ __forceinline__ double key_max(double a, double b) {
+#if MPCQP_KEY_BARE
+  double r;
+  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+#else
+  return fmax(a, b);
+#endif
+}
+__device__ __forceinline__ double key_min(double a, double b) {
+#if MPCQP_KEY_BARE
+  double r;
+  asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+#else
+  return fmin(a, b);
+#endif
+}
+template <int CTRL>
+__device__ __forceinline__ void dpp_keymax(double& key) {
+  key = key_max(key, dpp<CTRL>(key));
+}
+template <int CTRL>
+__device__ __forceinline__ void dpp_keymin(double& key) {
+  key = key_min(key, dpp<CTRL>(key));
+}
+
 // Row ownership: which lanes hold the row-indexed vectors of the box active
 // set (z, the multipliers, the states, the bounds and their scales).
 //   replicated  every lane of a row block holds all BS rows of the block and
@@ -366,9 +459,12 @@ struct QRowOwned<QSym<T, BS>> {
   static constexpr bool v = MPCQP_ROW_OWNER != 0;
 };
 
-template <class Mat, bool OWN_ROWS = QRowOwned<Mat>::v>
+// KEY: keyed reductions where the layout has them (QKeyed); a kernel passes
+// false to keep one instantiation on the compare-and-select reductions.
+template <class Mat, bool OWN_ROWS = QRowOwned<Mat>::v, bool KEY = true>
 struct RowOwn {  // replicated
   static constexpr bool OWNED = false;
+  static constexpr bool KEYED = false;
   static constexpr int BS = Mat::RPL;
   static constexpr int RO = BS;
   // slot s holds a row; its matrix row, to compare with a pivot (-1: none)
@@ -398,8 +494,8 @@ struct RowOwn {  // replicated
   }
 };
 
-template <class Mat>
-struct RowOwn<Mat, true> {  // owned (QSym)
+template <class Mat, bool KEY>
+struct RowOwn<Mat, true, KEY> {  // owned (QSym)
   static constexpr bool OWNED = true;
   static constexpr int BS = Mat::RPL;
   static constexpr int RO = Mat::RO;
@@ -445,6 +541,21 @@ struct RowOwn<Mat, true> {  // owned (QSym)
     dpp_argmin<0x4E>(v, idx);
     group_argmin(v, idx);
   }
+  // the same reductions on one key (QKeyed)
+  static constexpr bool KEYED = KEY && QKeyed<Mat>::v;
+  using K = Key<key_bits(Mat::NMAX)>;
+  static __device__ __forceinline__ void keymax(double& key) {
+    dpp_keymax<0xB1>(key);
+    dpp_keymax<0x4E>(key);
+    dpp_keymax<0x124>(key);
+    dpp_keymax<0x128>(key);
+  }
+  static __device__ __forceinline__ void keymin(double& key) {
+    dpp_keymin<0xB1>(key);
+    dpp_keymin<0x4E>(key);
+    dpp_keymin<0x124>(key);
+    dpp_keymin<0x128>(key);
+  }
   template <typename T>
   static __device__ __forceinline__ T column(Mat& M, int k, T* gb, T (&colr)[BS],
                                              T (&colc)[Mat::NC], T (&cown)[RO]) {
@@ -484,6 +595,30 @@ __device__ __forceinline__ void qscan(const Mat& M, const int (&ri)[Own::RO],
   Own::argmax(M, viol, pi, zv);
 }
 
+// The same on one key (Own::KEYED); cmax = 2^KB-1-row of this lane's slots.
+// A slot that is not free, and a row without a finite bound (NaN: both fmax
+// skip it), pass the sentinel.  viol comes back with its low bits clear, so
+// viol > tol sees it to 2^-47 relative; pi is only meaningful when viol > 0.
+// z_p is not carried: a new pivot reads it from the owners' LDS copy.
+template <class Own>
+__device__ __forceinline__ void qscan_key(const int (&cmax)[Own::RO], const int (&st)[Own::RO],
+                                          const double (&zr)[Own::RO],
+                                          const QBounds<double, Own::RO>& B, double& viol,
+                                          int& pi) {
+  using K = typename Own::K;
+  double key = -K::big();
+#pragma unroll
+  for (int r = 0; r < Own::RO; ++r) {
+    const double vl = (B.lo[r] - zr[r]) * B.sl[r];  // NaN for an infinite bound
+    const double vu = (zr[r] - B.hi[r]) * B.su[r];
+    const double v = fmin(fmax(fmax(vl, vu), -K::big()), K::big());
+    key = key_max(key, K::pack((st[r] == 0) ? v : -K::big(), cmax[r]));
+  }
+  Own::keymax(key);
+  viol = K::clear(key);
+  pi = int(K::MASK) - K::code(key);
+}
+
 
 // WARM: st (this lane's rows: 0 free, 1 at lb, 2 at ub, 3 padding) is the
 // starting active set and M the matrix swept on its free rows (H swept on F
@@ -505,6 +640,18 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
   }
   QBounds<T, RO> B;
   B.load(mi, lbs, ubs);
+  // keyed reductions (Own::KEYED): the index codes of this lane's slots, and
+  // the owners' copy of z in the group's LDS block (GBoxLds::oZ)
+  constexpr bool KEYED = Own::KEYED;
+  [[maybe_unused]] int cmin[RO], cmax[RO];
+  [[maybe_unused]] T* zs = gb + GBoxLds<Mat>::oZ;
+  if constexpr (KEYED) {
+#pragma unroll
+    for (int r = 0; r < RO; ++r) {
+      cmin[r] = mi[r];
+      cmax[r] = int(Own::K::MASK) - mi[r];
+    }
+  }
   // (replicated: the caller's arrays themselves)
   T zown[Own::OWNED ? RO : 1], mu[RO];
   int stown[Own::OWNED ? RO : 1];
@@ -534,6 +681,11 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
       zr[r] = (st[r] == 0) ? s[r] : zr[r];
       mu[r] = (st[r] == 1) ? g : ((st[r] == 2) ? -g : T(0));
     }
+    if constexpr (KEYED) {
+#pragma unroll
+      for (int r = 0; r < RO; ++r)
+        if (Own::has(M, r)) zs[mi[r]] = zr[r];
+    }
   };
   refresh();
   bool active = live;
@@ -543,15 +695,30 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
     while (true) {
       T mv = Lim<T>::inf();
       int k = 0;
+      if constexpr (KEYED) {
+        // negative candidates: the larger code is the more negative key
+        using K = typename Own::K;
+        T key = K::big();
 #pragma unroll
-      for (int r = 0; r < RO; ++r) {
-        const bool a = (st[r] == 1 || st[r] == 2) && mu[r] < -tol;
-        const bool take = a && mu[r] < mv;
-        mv = take ? mu[r] : mv;
-        k = take ? ri[r] : k;
+        for (int r = 0; r < RO; ++r) {
+          const bool a = (st[r] == 1 || st[r] == 2) && mu[r] < -tol;
+          key = key_min(key, K::pack(a ? fmax(mu[r], -K::big()) : K::big(), cmax[r]));
+        }
+        Own::keymin(key);
+        mv = K::clear(key);
+        k = int(K::MASK) - K::code(key);
+        drop = drop && mv < K::big();
+      } else {
+#pragma unroll
+        for (int r = 0; r < RO; ++r) {
+          const bool a = (st[r] == 1 || st[r] == 2) && mu[r] < -tol;
+          const bool take = a && mu[r] < mv;
+          mv = take ? mu[r] : mv;
+          k = take ? ri[r] : k;
+        }
+        Own::argmin(M, mv, k);
+        drop = drop && mv < Lim<T>::inf();
       }
-      Own::argmin(M, mv, k);
-      drop = drop && mv < Lim<T>::inf();
       if (!__any(drop)) break;
       if (drop && ++iters > max_iter) {
         code = MPCQP_STATUS_MAXITER;
@@ -585,7 +752,7 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
 #endif
     while (true) {
       if (__any(active && need_p)) {
-        T viol, zv;
+        T viol, zv = T(0);  // (keyed: z_p comes from LDS, zv stays unused)
         int pi;
 #if MPCQP_SCAN_AHEAD
         if (have_scan) {
@@ -593,18 +760,21 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
           pi = a_pi;
           zv = a_zv;
         } else {
-          qscan<T, Own>(M, ri, st, zr, B, viol, pi, zv);
+          if constexpr (KEYED) qscan_key<Own>(cmax, st, zr, B, viol, pi);
+          else qscan<T, Own>(M, ri, st, zr, B, viol, pi, zv);
         }
 #else
-        qscan<T, Own>(M, ri, st, zr, B, viol, pi, zv);
+        if constexpr (KEYED) qscan_key<Own>(cmax, st, zr, B, viol, pi);
+        else qscan<T, Own>(M, ri, st, zr, B, viol, pi, zv);
 #endif
         if (active && need_p) {
           if (!(viol > tol)) {
             active = false;  // settled (pending the exact re-check)
           } else {
             p = pi;
-            zp = zv;
+            if constexpr (!KEYED) zp = zv;
             const T lbp = lbs[p], ubp = ubs[p];
+            if constexpr (KEYED) zp = zs[p];
             side = (zp < lbp) ? 1 : 2;
             tgt = (side == 1) ? lbp : ubp;
             gp = T(0);
@@ -628,17 +798,40 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
       const T t2 = fabs(tgt - zp);
       T ti = Lim<T>::inf();
       int k = 0;
+      if constexpr (KEYED) {
+        // ti comes back with its low bits clear: ti < t2 sees it to 2^-47
+        // relative and a partial step has that length.  Neither reaches the
+        // result: the sweeps do not depend on step lengths, and z and the
+        // multipliers come from the exact refresh() of the final active set.
+        // (fmin maps an infinite or NaN ratio to the sentinel as well; two
+        // bit-equal negative ratios, which only rounding in the multipliers
+        // produces, resolve to the larger index)
+        using K = typename Own::K;
+        T key = K::big();
 #pragma unroll
-      for (int r = 0; r < RO; ++r) {
-        const T cs = co[r] * rm;  // dz per unit move of z_p (c stays raw for the sweep)
-        const T dmu = ((st[r] == 1) ? -cs : ((st[r] == 2) ? cs : T(0))) * sgn;
-        const bool cand = (st[r] == 1 || st[r] == 2) && dmu < T(0);
-        const T t = cand ? -mu[r] * fast_rcp(dmu) : Lim<T>::inf();
-        const bool take = t < ti;
-        ti = take ? t : ti;
-        k = take ? ri[r] : k;
+        for (int r = 0; r < RO; ++r) {
+          const T cs = co[r] * rm;
+          const T dmu = ((st[r] == 1) ? -cs : ((st[r] == 2) ? cs : T(0))) * sgn;
+          const bool cand = (st[r] == 1 || st[r] == 2) && dmu < T(0);
+          const T t = cand ? fmin(-mu[r] * fast_rcp(dmu), K::big()) : K::big();
+          key = key_min(key, K::pack(t, cmin[r]));
+        }
+        Own::keymin(key);
+        ti = K::clear(key);
+        k = K::code(key);
+      } else {
+#pragma unroll
+        for (int r = 0; r < RO; ++r) {
+          const T cs = co[r] * rm;  // dz per unit move of z_p (c stays raw for the sweep)
+          const T dmu = ((st[r] == 1) ? -cs : ((st[r] == 2) ? cs : T(0))) * sgn;
+          const bool cand = (st[r] == 1 || st[r] == 2) && dmu < T(0);
+          const T t = cand ? -mu[r] * fast_rcp(dmu) : Lim<T>::inf();
+          const bool take = t < ti;
+          ti = take ? t : ti;
+          k = take ? ri[r] : k;
+        }
+        Own::argmin(M, ti, k);
       }
-      Own::argmin(M, ti, k);
       const bool partial = ti < t2;
       const T s_eff = stepping ? (partial ? ti : t2) : T(0);
 #pragma unroll
@@ -691,7 +884,13 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
         code = MPCQP_STATUS_NOT_CONVEX;
         active = false;
       }
-      qscan<T, Own>(M, ri, st, zr, B, a_viol, a_pi, a_zv);
+      if constexpr (KEYED) {
+#pragma unroll
+        for (int r = 0; r < RO; ++r)
+          if (Own::has(M, r)) zs[mi[r]] = zr[r];
+      }
+      if constexpr (KEYED) qscan_key<Own>(cmax, st, zr, B, a_viol, a_pi);
+      else qscan<T, Own>(M, ri, st, zr, B, a_viol, a_pi, a_zv);
       have_scan = true;
       if (stepping && !bad) M.sweep_col(idx, sigma, d, kr, kcol);
       MPCQP_PHASE(7);
@@ -713,6 +912,11 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
         }
         need_p = !partial;
       }
+      if constexpr (KEYED) {
+#pragma unroll
+        for (int r = 0; r < RO; ++r)
+          if (Own::has(M, r)) zs[mi[r]] = zr[r];
+      }
       MPCQP_PHASE(7);
       if (bad) {
         code = MPCQP_STATUS_NOT_CONVEX;
@@ -722,9 +926,10 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
     }
     // exact refresh for every group, then re-check the bounds
     refresh();
-    T viol, zv;
+    T viol, zv = T(0);
     int pi;
-    qscan<T, Own>(M, ri, st, zr, B, viol, pi, zv);
+    if constexpr (KEYED) qscan_key<Own>(cmax, st, zr, B, viol, pi);
+    else qscan<T, Own>(M, ri, st, zr, B, viol, pi, zv);
     active = live && code == MPCQP_STATUS_OPTIMAL && viol > tol;
     if (!__any(active)) break;
   }

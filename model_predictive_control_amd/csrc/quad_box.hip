@@ -166,6 +166,14 @@ struct QMpcOwned {
       QRowOwned<Mat>::v && !(sizeof(T) == 8 && NX == 4 && NU == 2 && Mat::RPL == 5);
 };
 
+// Keyed reductions (Key, quad.hpp) per instantiation.  fp64 NX = 4 NU = 2 BS = 4
+// sits at 256 VGPRs and its scratch would grow from 52 to 60 bytes per lane:
+// it keeps the compare-and-select reductions.
+template <typename T, int NX, int NU, class Mat>
+struct QMpcKeyed {
+  static constexpr bool v = !(sizeof(T) == 8 && NX == 4 && NU == 2 && Mat::RPL == 4);
+};
+
 template <typename T, int NX, int NU, class Mat>
 struct QMpcLds {
   static constexpr bool ROWS = QMpcRows<T, NX, NU, Mat::RPL>::v;
@@ -853,7 +861,7 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
   else if ((__ballot(badbox) & gmask) != 0) code = MPCQP_STATUS_INFEASIBLE;
   T zr[RPL];
   int iters = 0;
-  using Own = RowOwn<Mat, QMpcOwned<T, NX, NU, Mat>::v>;
+  using Own = RowOwn<Mat, QMpcOwned<T, NX, NU, Mat>::v, QMpcKeyed<T, NX, NU, Mat>::v>;
   const int c2 = gi_box<T, RPL, Mat, Own>(M, gb, fs, lbs, ubs, n, a.max_iter, a.tol,
                                           live && code == MPCQP_STATUS_OPTIMAL, zr,
                                           iters MPCQP_CLK_ARG);
