@@ -5,6 +5,7 @@
 
 #include <cmath>
 #include <limits>
+#include <type_traits>
 
 #include "../../include/mpcqp.h"
 
@@ -165,43 +166,42 @@ __device__ __forceinline__ double lane_step(double v) {
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
-// Arg-max over the wave: returns the largest value; ties resolve to the
-// smallest lane index.  Lanes that should not compete pass -inf.
-template <int X, typename T>
-__device__ __forceinline__ void argmax_step(T& v, int& idx) {
-  const T ov = lane_step<X>(v);
-  const int oi = lane_step<X>(idx);
-  const bool take = (ov > v) || (ov == v && oi < idx);
+// One step of an arg-max (MAX) / arg-min over (value, index[, payload]): Get
+// fetches the partner lane's copy (Xor<X>, or Dpp<CTRL> of sym2d.hpp) and the
+// larger (smaller) value stays, ties to the smaller index.  NaN never wins.
+// Plain selects on purpose: a helper or a lambda changes gi_box_st's registers.
+template <int X>
+struct Xor {
+  template <typename V> static __device__ __forceinline__ V get(V v) { return lane_step<X>(v); }
+};
+struct NoPay {};  // P when the payload is left out
+template <bool MAX, class Get, typename T, typename P = NoPay>
+__device__ __forceinline__ void arg_step(T& v, int& idx, P&& pay = NoPay{}) {
+  constexpr bool PAY = !std::is_same_v<P, NoPay>;
+  const T ov = Get::get(v);
+  const int oi = Get::get(idx);
+  [[maybe_unused]] T op;
+  if constexpr (PAY) op = Get::get(pay);  // every lane fetches, whoever wins
+  const bool take = (MAX ? ov > v : ov < v) || (ov == v && oi < idx);
   v = take ? ov : v;
   idx = take ? oi : idx;
-}
-template <int X, typename T>
-__device__ __forceinline__ void argmin_step(T& v, int& idx) {
-  const T ov = lane_step<X>(v);
-  const int oi = lane_step<X>(idx);
-  const bool take = (ov < v) || (ov == v && oi < idx);
-  v = take ? ov : v;
-  idx = take ? oi : idx;
-}
-template <typename T>
-__device__ __forceinline__ void wave_argmax(T& v, int& idx) {
-  argmax_step<1>(v, idx);
-  argmax_step<2>(v, idx);
-  argmax_step<4>(v, idx);
-  argmax_step<8>(v, idx);
-  argmax_step<16>(v, idx);
-  argmax_step<32>(v, idx);
+  if constexpr (PAY) pay = take ? op : pay;
 }
 
-template <typename T>
-__device__ __forceinline__ void wave_argmin(T& v, int& idx) {
-  argmin_step<1>(v, idx);
-  argmin_step<2>(v, idx);
-  argmin_step<4>(v, idx);
-  argmin_step<8>(v, idx);
-  argmin_step<16>(v, idx);
-  argmin_step<32>(v, idx);
+// Arg-max / arg-min over the wave; ties to the smaller index.  Non-competing lanes pass -/+inf.
+template <bool MAX, typename T>
+__device__ __forceinline__ void wave_arg(T& v, int& idx) {
+  arg_step<MAX, Xor<1>>(v, idx);
+  arg_step<MAX, Xor<2>>(v, idx);
+  arg_step<MAX, Xor<4>>(v, idx);
+  arg_step<MAX, Xor<8>>(v, idx);
+  arg_step<MAX, Xor<16>>(v, idx);
+  arg_step<MAX, Xor<32>>(v, idx);
 }
+template <typename T>
+__device__ __forceinline__ void wave_argmax(T& v, int& idx) { wave_arg<true>(v, idx); }
+template <typename T>
+__device__ __forceinline__ void wave_argmin(T& v, int& idx) { wave_arg<false>(v, idx); }
 
 template <typename T>
 __device__ __forceinline__ T wave_max(T v) {

@@ -35,7 +35,7 @@
 // instantiation) starts every step from the empty set.
 #include <type_traits>
 
-#include "quad.hpp"
+#include "gi_box_core.hpp"
 #include "quad_api.hpp"
 
 namespace mpcqp {
@@ -73,10 +73,10 @@ using LoopArgsOf = std::conditional_t<AFFINE, LoopAffineArgs<T>, LoopArgs<T>>;
 
 template <typename T, int NX, int NU, int BS>
 struct LoopLds {
-  using Box = QBoxLds<T, BS>;
+  using Box = BoxLds<QSym<T, BS>>;
   static constexpr int NMAX = 4 * BS;
   static constexpr int PMAX = NMAX * (NMAX + 1) / 2;
-  static constexpr int oP = Box::size;          // packed H
+  static constexpr int oP = Box::oEnd;          // packed H
   static constexpr int oF = oP + PMAX;          // F, NMAX x NX
   static constexpr int oA = oF + NMAX * NX;     // A, NX x NX
   static constexpr int oB = oA + NX * NX;       // B, NX x NU
@@ -94,7 +94,7 @@ struct LoopOcc {
   static constexpr int w = BS <= 2 ? 4 : 1;
 };
 
-// Keyed reductions (Key, quad.hpp) per instantiation.  The affine fp64 NX = 4
+// Keyed reductions (Key, gi_box_core.hpp) per instantiation.  The affine fp64 NX = 4
 // NU = 2 BS = 5 kernel sits at 256 VGPRs and would take one AGPR more (257: the
 // bound of its registers 2 -> 1 waves): it keeps the compare-and-select
 // reductions.
@@ -137,7 +137,7 @@ template <typename T, int NX, int NU, int BS, bool AFFINE = false>
 __global__ __launch_bounds__(64, (LoopOcc<T, BS>::w)) void box_loop_kernel(
     LoopArgsOf<T, AFFINE> a) {
   using Lq = LoopLds<T, NX, NU, BS>;
-  using Box = QBoxLds<T, BS>;
+  using Box = BoxLds<QSym<T, BS>>;
   constexpr int NMAX = Lq::NMAX;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const int lane = threadIdx.x, g = lane >> 4, q = lane & 15;
@@ -327,9 +327,9 @@ __global__ __launch_bounds__(64, (LoopOcc<T, BS>::w)) void box_loop_kernel(
     T zr[BS];
     int iters = 0;
     using Own = RowOwn<QSym<T, BS>, QRowOwned<QSym<T, BS>>::v, LoopKeyed<T, NX, NU, BS, AFFINE>::v>;
-    const int c2 = gi_box_st<T, BS, true, QSym<T, BS>, Own>(M, gb, fs, lbs, ubs, n, a.max_iter, a.tol,
-                                          live && code == MPCQP_STATUS_OPTIMAL, zr, iters, st
-                                          MPCQP_CLK_ARG);
+    const int c2 = gi_box_st<true, Own>(M, gb, fs, lbs, ubs, n, a.max_iter, a.tol,
+                                        live && code == MPCQP_STATUS_OPTIMAL, zr, iters,
+                                        st MPCQP_CLK_ARG);
     if (code == MPCQP_STATUS_OPTIMAL) code = c2;
     const bool okc = code == MPCQP_STATUS_OPTIMAL || code == MPCQP_STATUS_MAXITER;
     if (!okc) {

@@ -60,7 +60,7 @@ struct MpcLds {
   int oA, oB, oQ, oQf, oR, oC, oX0, oK, oSi, oAcl, oX, oKf, oMinv, total, ld;
   __host__ __device__ MpcLds(int N, int n, int tv) {
     const int S = tv ? N : 1;
-    oA = BoxLds<T, BS>::oEnd;
+    oA = BoxLds<Sym2D<T, BS>>::oEnd;
     oB = oA + S * NX * NX;
     oQ = oB + S * NX * NU;
     oQf = oQ + NX * NX;
@@ -88,7 +88,7 @@ __device__ __forceinline__ void load_sq(const T* s, T (&m)[NX][NU], int ld) {
 
 template <typename T, int NX, int NU, int BS>
 __global__ __launch_bounds__(64, (MpcOcc<NX, BS>::w)) void mpc_box_kernel(MpcBoxArgs<T> a) {
-  using BL = BoxLds<T, BS>;
+  using BL = BoxLds<Sym2D<T, BS>>;
   constexpr int NMAX = BL::NMAX;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   T* sm = reinterpret_cast<T*>(smem_raw);
@@ -437,7 +437,7 @@ __global__ __launch_bounds__(64, (MpcOcc<NX, BS>::w)) void mpc_box_kernel(MpcBox
   if (__any(nonfinite)) code = MPCQP_STATUS_NONFINITE;
   else if (__any(badbox)) code = MPCQP_STATUS_INFEASIBLE;
   if (code == MPCQP_STATUS_OPTIMAL)
-    code = gi_box_core<T, BS>(M, buf, fs, lbs, ubs, n, a.max_iter, a.tol, zr, iters);
+    code = gi_box_core(M, buf, fs, lbs, ubs, n, a.max_iter, a.tol, zr, iters);
   if (code != MPCQP_STATUS_OPTIMAL && code != MPCQP_STATUS_MAXITER) {
 #pragma unroll
     for (int r = 0; r < BS; ++r) zr[r] = __builtin_nan("");

@@ -34,11 +34,11 @@
 //      that yields f_k = B_k'y_{k+1};
 //   4. M = -W~ W~' accumulated from the LDS tile straight into the register
 //      blocks, bitwise symmetric;
-//   5. Goldfarb-Idnani on M (quad.hpp).
+//   5. Goldfarb-Idnani on M (gi_box_core.hpp).
 // (mpc_box.hip, the one-QP-per-wave path, builds the columns of H^{-1} one by
 // one instead and serves as the independent comparator in the tests.)
 #include "mpc_factor.hpp"
-#include "quad.hpp"
+#include "gi_box_core.hpp"
 #include "quad_api.hpp"
 
 namespace mpcqp {
@@ -55,10 +55,10 @@ __global__ __launch_bounds__(64, (QuadOcc<T, BS>::w)) void box_quad_kernel(BoxAr
 #ifdef MPCQP_PHASE_TIMING
   PhaseClock mpcqp_clk;
 #endif
-  using L = QBoxLds<T, BS>;
+  using L = BoxLds<QSym<T, BS>>;
   constexpr int NMAX = L::NMAX;
   constexpr int PMAX = NMAX * (NMAX + 1) / 2;
-  constexpr int GSZ = L::size + PMAX;
+  constexpr int GSZ = L::oEnd + PMAX;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const int lane = threadIdx.x, g = lane >> 4, q = lane & 15;
   const int b = blockIdx.x * 4 + g;
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(64, (QuadOcc<T, BS>::w)) void box_quad_kernel(BoxAr
   T* fs = gs + L::oF;
   T* lbs = gs + L::oLb;
   T* ubs = gs + L::oUb;
-  T* Ps = gs + L::size;
+  T* Ps = gs + L::oEnd;
   {
     constexpr int MAXT = (PMAX + 15) / 16;
     const T* Hb = a.H + (int64_t)bl * a.sH;
@@ -117,8 +117,8 @@ __global__ __launch_bounds__(64, (QuadOcc<T, BS>::w)) void box_quad_kernel(BoxAr
   if (code == MPCQP_STATUS_OPTIMAL && !ok) code = MPCQP_STATUS_NOT_CONVEX;
   T zr[BS];
   int iters = 0;
-  const int c2 = gi_box<T, BS>(M, gb, fs, lbs, ubs, n, a.max_iter, a.tol,
-                                    live && code == MPCQP_STATUS_OPTIMAL, zr, iters MPCQP_CLK_ARG);
+  const int c2 = gi_box(M, gb, fs, lbs, ubs, n, a.max_iter, a.tol,
+                        live && code == MPCQP_STATUS_OPTIMAL, zr, iters MPCQP_CLK_ARG);
   if (code == MPCQP_STATUS_OPTIMAL) code = c2;
   if (code != MPCQP_STATUS_OPTIMAL && code != MPCQP_STATUS_MAXITER) {
 #pragma unroll
@@ -157,7 +157,7 @@ struct QMpcRows {
   static constexpr bool v = NX <= 2 && !(sizeof(T) == 8 && NU == 2 && BS <= 3);
 };
 
-// Row ownership of the box active set (RowOwn, quad.hpp) per instantiation.
+// Row ownership of the box active set (RowOwn, gi_box_core.hpp) per instantiation.
 // fp64 NX = 4 NU = 2 BS = 5 sits at 256 VGPRs either way and its scratch would
 // grow from 52 to 56 bytes per lane: it keeps the replicated vectors.
 template <typename T, int NX, int NU, class Mat>
@@ -166,7 +166,7 @@ struct QMpcOwned {
       QRowOwned<Mat>::v && !(sizeof(T) == 8 && NX == 4 && NU == 2 && Mat::RPL == 5);
 };
 
-// Keyed reductions (Key, quad.hpp) per instantiation.  fp64 NX = 4 NU = 2 BS = 4
+// Keyed reductions (Key, gi_box_core.hpp) per instantiation.  fp64 NX = 4 NU = 2 BS = 4
 // sits at 256 VGPRs and its scratch would grow from 52 to 60 bytes per lane:
 // it keeps the compare-and-select reductions.
 template <typename T, int NX, int NU, class Mat>
@@ -188,7 +188,7 @@ struct QMpcLds {
   __host__ __device__ QMpcLds(int N, int n, int tv) {
     const int S = tv ? N : 1;
     const int N2 = ROWS ? 0 : N;
-    oA = GBoxLds<Mat>::size;
+    oA = BoxLds<Mat>::oEnd;
     oB = oA + S * NX * NX;
     oQ = oB + S * NX * NU;
     oQf = oQ + NX * NX;
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
 #ifdef MPCQP_WAVE_CLOCK
   const unsigned long long wclk0 = __builtin_amdgcn_s_memrealtime();
 #endif
-  using BL = GBoxLds<Mat>;
+  using BL = BoxLds<Mat>;
   constexpr int NV = BL::NV;
   constexpr int RPL = Mat::RPL;
   constexpr int GPW = kWave / GL;
@@ -862,9 +862,8 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
   T zr[RPL];
   int iters = 0;
   using Own = RowOwn<Mat, QMpcOwned<T, NX, NU, Mat>::v, QMpcKeyed<T, NX, NU, Mat>::v>;
-  const int c2 = gi_box<T, RPL, Mat, Own>(M, gb, fs, lbs, ubs, n, a.max_iter, a.tol,
-                                          live && code == MPCQP_STATUS_OPTIMAL, zr,
-                                          iters MPCQP_CLK_ARG);
+  const int c2 = gi_box<Own>(M, gb, fs, lbs, ubs, n, a.max_iter, a.tol,
+                             live && code == MPCQP_STATUS_OPTIMAL, zr, iters MPCQP_CLK_ARG);
   if (code == MPCQP_STATUS_OPTIMAL) code = c2;
   MPCQP_PHASE(4);
 #ifdef MPCQP_PHASE_TIMING
@@ -903,9 +902,9 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
 // ------------------------------------------------------------- launchers
 template <typename T, int BS>
 int launch_box_quad(const BoxArgsQ<T>& a, hipStream_t st) {
-  using L = QBoxLds<T, BS>;
+  using L = BoxLds<QSym<T, BS>>;
   constexpr int NMAX = L::NMAX;
-  const size_t bytes = (size_t)4 * (L::size + NMAX * (NMAX + 1) / 2) * sizeof(T);
+  const size_t bytes = (size_t)4 * (L::oEnd + NMAX * (NMAX + 1) / 2) * sizeof(T);
   hipLaunchKernelGGL((box_quad_kernel<T, BS>), dim3((a.batch + 3) / 4), dim3(kWave), bytes, st, a);
   MPCQP_CHECK_LAUNCH("box_quad_kernel");
   return MPCQP_OK;

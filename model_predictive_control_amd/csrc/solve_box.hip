@@ -39,7 +39,7 @@ struct BoxArgs {
 
 template <typename T, int BS>
 __global__ __launch_bounds__(64, BoxOcc<BS>::w) void box_gi_kernel(BoxArgs<T> a) {
-  using L = BoxLds<T, BS>;
+  using L = BoxLds<Sym2D<T, BS>>;
   constexpr int NMAX = L::NMAX;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   T* sm = reinterpret_cast<T*>(smem_raw);
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(64, BoxOcc<BS>::w) void box_gi_kernel(BoxArgs<T> a)
       }
     }
     if (code == MPCQP_STATUS_OPTIMAL)
-      code = gi_box_core<T, BS>(M, buf, fs, lbs, ubs, n, a.max_iter, a.tol, zr, iters);
+      code = gi_box_core(M, buf, fs, lbs, ubs, n, a.max_iter, a.tol, zr, iters);
   }
   if (code != MPCQP_STATUS_OPTIMAL && code != MPCQP_STATUS_MAXITER) {
 #pragma unroll
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(64, BoxOcc<BS>::w) void box_gi_kernel(BoxArgs<T> a)
 
 template <typename T, int BS>
 static int launch_box(const BoxArgs<T>& a, hipStream_t st) {
-  const size_t bytes = (size_t)(BoxLds<T, BS>::oEnd + a.n * (a.n + 1) / 2) * sizeof(T);
+  const size_t bytes = (size_t)(BoxLds<Sym2D<T, BS>>::oEnd + a.n * (a.n + 1) / 2) * sizeof(T);
   hipLaunchKernelGGL((box_gi_kernel<T, BS>), dim3(a.batch), dim3(kWave), bytes, st, a);
   MPCQP_CHECK_LAUNCH("box_gi_kernel");
   return MPCQP_OK;

@@ -11,8 +11,6 @@
 #pragma once
 #include "common.hpp"
 
-#include <type_traits>
-
 namespace mpcqp {
 
 // ---------------------------------------------------------------- DPP
@@ -45,60 +43,12 @@ __device__ __forceinline__ T rowblock_sum(T v) {
   return v;
 }
 
-// Reduce a (value, index) pair across the 8 row blocks (lanes differing in
-// bits 3..5).  Lanes within one row block hold identical candidates.
-// Arg-max: larger value wins, ties to the smaller index.  NaN never wins.
-template <typename T>
-__device__ __forceinline__ void blocks_argmax(T& v, int& idx) {
-  {
-    const T ov = dpp<0x128>(v);
-    const int oi = dpp<0x128>(idx);
-    const bool take = (ov > v) || (ov == v && oi < idx);
-    v = take ? ov : v;
-    idx = take ? oi : idx;
-  }
-  argmax_step<16>(v, idx);
-  argmax_step<32>(v, idx);
-}
-
-// Same with a payload value carried along with the winner.
-template <typename T>
-__device__ __forceinline__ void blocks_argmax(T& v, int& idx, T& pay) {
-  {
-    const T ov = dpp<0x128>(v);
-    const int oi = dpp<0x128>(idx);
-    const T op = dpp<0x128>(pay);
-    const bool take = (ov > v) || (ov == v && oi < idx);
-    v = take ? ov : v;
-    idx = take ? oi : idx;
-    pay = take ? op : pay;
-  }
-  auto step = [&](auto x) __attribute__((always_inline)) {
-    constexpr int X = decltype(x)::value;
-    const T ov = lane_step<X>(v);
-    const int oi = lane_step<X>(idx);
-    const T op = lane_step<X>(pay);
-    const bool take = (ov > v) || (ov == v && oi < idx);
-    v = take ? ov : v;
-    idx = take ? oi : idx;
-    pay = take ? op : pay;
-  };
-  step(std::integral_constant<int, 16>{});
-  step(std::integral_constant<int, 32>{});
-}
-
-template <typename T>
-__device__ __forceinline__ void blocks_argmin(T& v, int& idx) {
-  {
-    const T ov = dpp<0x128>(v);
-    const int oi = dpp<0x128>(idx);
-    const bool take = (ov < v) || (ov == v && oi < idx);
-    v = take ? ov : v;
-    idx = take ? oi : idx;
-  }
-  argmin_step<16>(v, idx);
-  argmin_step<32>(v, idx);
-}
+// A DPP control word as the fetch of a reduction step (arg_step, common.hpp).
+template <int CTRL>
+struct Dpp {
+  template <typename V>
+  static __device__ __forceinline__ V get(V v) { return dpp<CTRL>(v); }
+};
 
 // NOTE: no helper here indexes a register array with a runtime value --
 // hipcc turns such selects into scratch-memory indexing (guide rule 20).
@@ -119,6 +69,38 @@ struct Sym2D {
   __device__ __forceinline__ void init(int lane) {
     bi = lane >> 3;
     bj = lane & 7;
+  }
+
+  // Arg-max (MAX) / arg-min of (value, index[, payload]) across the 8 row
+  // blocks (lanes differing in bits 3..5); the lanes of one row block hold
+  // identical candidates.
+  template <bool MAX>
+  static __device__ __forceinline__ void rows_arg(T& v, int& idx) {
+    arg_step<MAX, Dpp<0x128>>(v, idx);
+    arg_step<MAX, Xor<16>>(v, idx);
+    arg_step<MAX, Xor<32>>(v, idx);
+  }
+  // With a payload the two cross-row steps are arg_step written out in a
+  // lambda.  The compiler builds the selects of a captured reference as
+  // branches, and every one-QP-per-wave box kernel depends on it: with
+  // arg_step here 15 of the 16 box_gi_kernel instantiations change their
+  // registers or scratch (fp64 BS = 2: 96 -> 103 VGPRs, BS = 3: 100 -> 112
+  // bytes of scratch per lane).
+  template <bool MAX>
+  static __device__ __forceinline__ void rows_arg(T& v, int& idx, T& pay) {
+    arg_step<MAX, Dpp<0x128>>(v, idx, pay);
+    auto step = [&](auto get) __attribute__((always_inline)) {
+      using Get = decltype(get);
+      const T ov = Get::get(v);
+      const int oi = Get::get(idx);
+      const T op = Get::get(pay);
+      const bool take = (MAX ? ov > v : ov < v) || (ov == v && oi < idx);
+      v = take ? ov : v;
+      idx = take ? oi : idx;
+      pay = take ? op : pay;
+    };
+    step(Xor<16>{});
+    step(Xor<32>{});
   }
 
   // Fill from a packed-lower matrix staged in LDS; entries outside n x n are 0.

@@ -20,8 +20,10 @@ from oracle import qp as oq
 EPS32 = float(np.finfo(np.float32).eps)
 
 # (nx, nu, N): all three <NX, NU> instantiations of box_loop_kernel, block sizes
-# 1, 2 (four waves per SIMD), 6 and 8, padded states and inputs
-SHAPES = [(1, 1, 3), (2, 1, 8), (2, 2, 11), (4, 1, 32), (3, 2, 16), (4, 2, 2)]
+# 1, 2 (four waves per SIMD), 6 and 8, padded states and inputs; (4, 2, 10) is
+# n = 20, block size 5: the one fp64 instantiation whose warm-started solve
+# runs on the compare-and-select reductions (LoopKeyed, loop_box.hip)
+SHAPES = [(1, 1, 3), (2, 1, 8), (2, 2, 11), (4, 1, 32), (3, 2, 16), (4, 2, 2), (4, 2, 10)]
 FP32_SHAPES = [(2, 1, 8), (3, 2, 16), (4, 1, 32)]
 B, T = 5, 6          # a second wave with one live group
 _cache = {}
