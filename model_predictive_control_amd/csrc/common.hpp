@@ -264,4 +264,21 @@ __device__ __forceinline__ void lds_exchange() {
 
 inline size_t dtype_size(int dtype) { return dtype == MPCQP_F64 ? 8 : 4; }
 
+// Host side: the register-block instantiation for `rows` rows at PER rows per
+// block, BS = ceil(rows / PER) in 1..8 (callers refuse more rows than 8 PER
+// beforehand).  Calls f(std::integral_constant<int, BS>{}) and returns its result.
+template <int PER, class F>
+inline auto dispatch_bs(int rows, F&& f) {
+  switch ((rows + PER - 1) / PER) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    default: return f(std::integral_constant<int, 8>{});
+  }
+}
+
 }  // namespace mpcqp

@@ -423,16 +423,9 @@ static int launch_loop(const LoopArgsOf<T, AFFINE>& a, hipStream_t st) {
 
 template <typename T, int NX, int NU, bool AFFINE>
 static int loop_bs(const LoopArgsOf<T, AFFINE>& a, hipStream_t st) {
-  switch ((a.n + 3) / 4) {
-    case 1: return launch_loop<T, NX, NU, 1, AFFINE>(a, st);
-    case 2: return launch_loop<T, NX, NU, 2, AFFINE>(a, st);
-    case 3: return launch_loop<T, NX, NU, 3, AFFINE>(a, st);
-    case 4: return launch_loop<T, NX, NU, 4, AFFINE>(a, st);
-    case 5: return launch_loop<T, NX, NU, 5, AFFINE>(a, st);
-    case 6: return launch_loop<T, NX, NU, 6, AFFINE>(a, st);
-    case 7: return launch_loop<T, NX, NU, 7, AFFINE>(a, st);
-    default: return launch_loop<T, NX, NU, 8, AFFINE>(a, st);
-  }
+  return dispatch_bs<4>(a.n, [&](auto bs) {
+    return launch_loop<T, NX, NU, decltype(bs)::value, AFFINE>(a, st);
+  });
 }
 
 template <typename T, bool AFFINE>

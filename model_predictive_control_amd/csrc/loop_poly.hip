@@ -47,8 +47,8 @@
 // steps at once by poly_affine_prep_kernel before the loop and the loop only
 // adds them.  AFFINE is a template flag like SOFT: the four
 // instantiations without it compile to what they were.
+#include "dual_range_core.hpp"
 #include "poly_ws.hpp"
-#include "sym2d.hpp"
 
 // Steps between two rebuilds of W from M ("Poly loop").
 #ifndef MPCQP_POLY_LOOP_REBUILD
@@ -109,23 +109,6 @@ __host__ __device__ inline int poly_loop_lds(int BS, int mt, int nx, int nu) {
   const int NMAX = 8 * BS;
   return NMAX * BS + NMAX + 8 * NMAX + mt * (mt + 1) / 2 + 2 * nx * NMAX + nx * nx + nx * nu +
          NMAX * nu + nx * nu + 32;
-}
-
-// z_j = Kt[:, j]' x - sum over the rows with y != 0 of Ut[r][j] y_r: the
-// epilogue of dual_range_kernel.  One function for the plan (global Ut, Kt)
-// and for the applied input (their LDS copies), so that u_t equals z_t[0..nu)
-// bit for bit.
-// z0: the state-independent part of the plan (-Hinv g_t)_j, 0 without one.
-template <typename T>
-__device__ __forceinline__ T poly_epilogue(const T* Kt, const T* Ut, int64_t ld, int j, int nx,
-                                           const T* x, T yi, uint64_t yact, T z0 = T(0)) {
-  T acc = z0;
-  for (int k = 0; k < nx; ++k) acc = fma(Kt[(int64_t)k * ld + j], x[k], acc);
-  for (uint64_t mk = yact; mk; mk &= mk - 1) {
-    const int r = uniform(__builtin_ctzll(mk));
-    acc = fma(-Ut[(int64_t)r * ld + j], readlane(yi, r), acc);
-  }
-  return acc;
 }
 
 // st: 0 inactive, 1 at lower, 2 at upper, 3 padding row; row-indexed vectors
@@ -229,7 +212,7 @@ __global__ __launch_bounds__(64) void poly_loop_kernel(PolyLoopArgsOf<T, SOFT, A
   int st = row ? 0 : 3;
   T yi = T(0), si = T(0);
   const T tol = a.tol;
-  const T dep_tol = sizeof(T) == 8 ? T(1e-10) : T(1e-5);
+  constexpr T dep_tol = kDualDepTol<T>;
   const int max_iter = a.max_iter;
   int failed = MPCQP_STATUS_OPTIMAL;  // code of the instance's first failed step
   bool reload = true;                 // W <- M at the top of the step ...
@@ -711,16 +694,9 @@ static int launch_poly_loop(const PolyLoopArgsOf<T, SOFT, AFFINE>& a, hipStream_
 
 template <typename T, bool SOFT, bool AFFINE = false>
 static int poly_loop_t(const PolyLoopArgsOf<T, SOFT, AFFINE>& a, hipStream_t st) {
-  switch ((a.mt + 7) / 8) {
-    case 1: return launch_poly_loop<T, 1, SOFT, AFFINE>(a, st);
-    case 2: return launch_poly_loop<T, 2, SOFT, AFFINE>(a, st);
-    case 3: return launch_poly_loop<T, 3, SOFT, AFFINE>(a, st);
-    case 4: return launch_poly_loop<T, 4, SOFT, AFFINE>(a, st);
-    case 5: return launch_poly_loop<T, 5, SOFT, AFFINE>(a, st);
-    case 6: return launch_poly_loop<T, 6, SOFT, AFFINE>(a, st);
-    case 7: return launch_poly_loop<T, 7, SOFT, AFFINE>(a, st);
-    default: return launch_poly_loop<T, 8, SOFT, AFFINE>(a, st);
-  }
+  return dispatch_bs<8>(a.mt, [&](auto bs) {
+    return launch_poly_loop<T, decltype(bs)::value, SOFT, AFFINE>(a, st);
+  });
 }
 
 // All three entry points: rho == nullptr is the hard loop; g == e == nullptr
@@ -772,8 +748,8 @@ static int poly_loop_entry(const char* who, int dtype, int batch, int n, int m, 
     a.lbz = nbox ? (const T*)lbz : nullptr; a.ubz = nbox ? (const T*)ubz : nullptr;
     a.w = (const T*)w;
     a.xs = (T*)xs; a.us = (T*)us; a.zs = (T*)zs; a.ys = (T*)ys; a.status = status;
-    a.max_iter = max_iter > 0 ? max_iter : 4 * mt + 40;
-    a.tol = tol > 0 ? (T)tol : (dtype == MPCQP_F64 ? (T)1e-12 : (T)1e-6);
+    a.max_iter = dual_max_iter(max_iter, mt);
+    a.tol = dual_tol<T>(tol);
   };
   auto run = [&](auto tp) {
     using T = decltype(tp);

@@ -912,16 +912,9 @@ int launch_box_quad(const BoxArgsQ<T>& a, hipStream_t st) {
 
 template <typename T>
 int solve_box_quad(const BoxArgsQ<T>& a, hipStream_t st) {
-  switch ((a.n + 3) / 4) {
-    case 1: return launch_box_quad<T, 1>(a, st);
-    case 2: return launch_box_quad<T, 2>(a, st);
-    case 3: return launch_box_quad<T, 3>(a, st);
-    case 4: return launch_box_quad<T, 4>(a, st);
-    case 5: return launch_box_quad<T, 5>(a, st);
-    case 6: return launch_box_quad<T, 6>(a, st);
-    case 7: return launch_box_quad<T, 7>(a, st);
-    default: return launch_box_quad<T, 8>(a, st);
-  }
+  return dispatch_bs<4>(a.n, [&](auto bs) {
+    return launch_box_quad<T, decltype(bs)::value>(a, st);
+  });
 }
 
 template <typename T, int NX, int NU, class Mat, int GL, int OCC>
@@ -953,16 +946,9 @@ int launch_mpc_quad(const MpcArgsQ<T>& a, hipStream_t st) {
 
 template <typename T, int NX, int NU>
 int mpc_quad_bs(const MpcArgsQ<T>& a, hipStream_t st) {
-  switch ((a.N * a.nu + 3) / 4) {
-    case 1: return launch_mpc_quad<T, NX, NU, 1>(a, st);
-    case 2: return launch_mpc_quad<T, NX, NU, 2>(a, st);
-    case 3: return launch_mpc_quad<T, NX, NU, 3>(a, st);
-    case 4: return launch_mpc_quad<T, NX, NU, 4>(a, st);
-    case 5: return launch_mpc_quad<T, NX, NU, 5>(a, st);
-    case 6: return launch_mpc_quad<T, NX, NU, 6>(a, st);
-    case 7: return launch_mpc_quad<T, NX, NU, 7>(a, st);
-    default: return launch_mpc_quad<T, NX, NU, 8>(a, st);
-  }
+  return dispatch_bs<4>(a.N * a.nu, [&](auto bs) {
+    return launch_mpc_quad<T, NX, NU, decltype(bs)::value>(a, st);
+  });
 }
 
 template <typename T>

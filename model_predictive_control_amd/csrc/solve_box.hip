@@ -129,16 +129,9 @@ static int solve_box_t(int batch, int n, const void* H, int64_t sH, const void* 
     BoxArgsQ<T> q{batch, n, a.H, sH, a.f, sf, a.lb, slb, a.ub, sub, a.z, status, a.max_iter, a.tol};
     return solve_box_quad<T>(q, st);
   }
-  switch ((n + 7) / 8) {
-    case 1: return launch_box<T, 1>(a, st);
-    case 2: return launch_box<T, 2>(a, st);
-    case 3: return launch_box<T, 3>(a, st);
-    case 4: return launch_box<T, 4>(a, st);
-    case 5: return launch_box<T, 5>(a, st);
-    case 6: return launch_box<T, 6>(a, st);
-    case 7: return launch_box<T, 7>(a, st);
-    default: return launch_box<T, 8>(a, st);
-  }
+  return dispatch_bs<8>(n, [&](auto bs) {
+    return launch_box<T, decltype(bs)::value>(a, st);
+  });
 }
 
 }  // namespace mpcqp

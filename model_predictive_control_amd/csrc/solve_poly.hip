@@ -28,8 +28,8 @@
 // pivot W_pp (its Schur complement -- zero when p depends on the active rows,
 // in which case a pure dual step drops rows first), dropping row k is a
 // reverse sweep.  Same register-resident sweep machinery as solve_box.hip.
+#include "dual_range_core.hpp"
 #include "poly_ws.hpp"
-#include "sym2d.hpp"
 
 namespace mpcqp {
 
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(64) void dual_range_kernel(DualArgs<T> a) {
   int code = MPCQP_STATUS_MAXITER;
   int iters = 0;
   const T tol = a.tol;
-  const T dep_tol = sizeof(T) == 8 ? T(1e-10) : T(1e-5);
+  constexpr T dep_tol = kDualDepTol<T>;
   const int max_iter = a.max_iter;
   if (*a.flag) {
     code = MPCQP_STATUS_NOT_CONVEX;
@@ -431,18 +431,9 @@ static int poly_solve_t(int batch, int n, int m, int nbox, int nx, const void* w
   a.f1 = (const T*)f1; a.sF1 = sF1;
   a.flag = (const int32_t*)(base + L.oFlag);
   a.z = (T*)z; a.y = (T*)y; a.status = status;
-  a.max_iter = max_iter > 0 ? max_iter : 4 * mt + 40;
-  a.tol = tol > 0 ? (T)tol : (sizeof(T) == 8 ? (T)1e-12 : (T)1e-6);
-  switch ((mt + 7) / 8) {
-    case 1: launch_dual<T, 1>(a, st); break;
-    case 2: launch_dual<T, 2>(a, st); break;
-    case 3: launch_dual<T, 3>(a, st); break;
-    case 4: launch_dual<T, 4>(a, st); break;
-    case 5: launch_dual<T, 5>(a, st); break;
-    case 6: launch_dual<T, 6>(a, st); break;
-    case 7: launch_dual<T, 7>(a, st); break;
-    default: launch_dual<T, 8>(a, st); break;
-  }
+  a.max_iter = dual_max_iter(max_iter, mt);
+  a.tol = dual_tol<T>(tol);
+  dispatch_bs<8>(mt, [&](auto bs) { launch_dual<T, decltype(bs)::value>(a, st); });
   MPCQP_CHECK_LAUNCH("dual_range_kernel");
   return MPCQP_OK;
 }

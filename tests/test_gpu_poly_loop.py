@@ -185,6 +185,58 @@ def test_config4_rows_on_the_plan(dev):
         pc.check_episode(qp, r["xs"], r["us"], r["zs"], i)
 
 
+# One shape per kernel instantiation, ceil(m_total / 8) = 1..8 with m_total =
+# m + (box ? N nu : 0); the fifth has more rows than variables (40 rows over
+# n = 20), so that dependent rows and the pure dual step are taken.
+# The last entry scales x0: 3 as in test_poly_parametric_x0, and 12 for the
+# three-row shape, where at 3 no instance needs a second iteration.
+COLD_SHAPES = [(2, 1, 4, 3, False, 12), (2, 1, 5, 6, True, 3), (3, 2, 5, 12, True, 3),
+               (4, 2, 6, 18, True, 3), (4, 2, 10, 40, False, 3), (4, 2, 8, 28, True, 3),
+               (4, 3, 8, 30, True, 3), (4, 4, 8, 30, True, 3)]
+COLD_PARTIAL = []       # per shape run so far: whether a partial step occurred
+
+
+@pytest.mark.parametrize("nx,nu,N,m,box,scale", COLD_SHAPES)
+def test_cold_first_step_is_poly_solve(dev, nx, nu, N, m, box, scale):
+    """Step 0 of a cold PolyQP.loop with E = None and no w is PolyQP.solve(x0)
+    on the same factors and bounds: dual_range_kernel and poly_loop_kernel run
+    the same dual range active set from the same start (W = M, empty set), so
+    zs[0] = z, ys[0] = y and the status words (code and iteration count) are
+    equal bit for bit (they are in all eight shapes).  Inputs as
+    in test_poly_parametric_x0 (random stable plant, rows G z <= h on the plan
+    with h > 0, optional input box), batch 8, T = 1, fp64.  Every shape has an
+    instance with two or more iterations, and over the shapes a partial step
+    occurs (iterations above the count of non-zero multipliers)."""
+    rng = np.random.default_rng(nx * 100 + N)
+    U, _ = np.linalg.qr(rng.normal(size=(nx, nx)))
+    A = (U * rng.uniform(0.5, 0.98, nx)) @ U.T
+    B = rng.normal(size=(nx, nu)) / np.sqrt(nx)
+    n = N * nu
+    d = oc.condense(A, B, np.eye(nx), 0.1 * np.eye(nu), np.eye(nx), N)
+    G = rng.normal(size=(m, n))
+    h = rng.uniform(0.5, 1.5, size=m)
+    X0 = rng.normal(size=(8, nx)) * scale
+    lbz, ubz = (-0.4, 0.4) if box else (None, None)
+    qp = batched.PolyQP(_t(oc.pack_lower(d["H"]), dev), _t(G, dev), _t(d["F"], dev), lbz, ubz)
+    assert (qp.mt + 7) // 8 == COLD_SHAPES.index((nx, nu, N, m, box, scale)) + 1
+    z, y, st = qp.solve(_t(X0, dev), None, hu=_t(h, dev))
+    r = _np(qp.loop(_t(A, dev), _t(B, dev), _t(X0, dev), 1, None, _t(h, dev), plans=True,
+                    multipliers=True, cold=True))
+    z, y, st = z.cpu().numpy(), y.cpu().numpy(), st.cpu().numpy()
+    iters = (st >> 8) & 0xFFFF
+    partial = iters > (y != 0).sum(axis=1)
+    COLD_PARTIAL.append(bool(partial.any()))
+    print(f"m_total={qp.mt}: iterations {iters.tolist()}, partial steps in {int(partial.sum())} "
+          f"instances, max|z - zs[0]| = {np.abs(z - r['zs'][0]).max():.3e}")
+    assert (st & 0xFF == OPT).all(), st & 0xFF
+    assert (iters >= 2).any(), iters
+    assert np.array_equal(st, r["status"][0])
+    assert np.array_equal(z, r["zs"][0])
+    assert np.array_equal(y, r["ys"][0])
+    if len(COLD_PARTIAL) == len(COLD_SHAPES):
+        assert any(COLD_PARTIAL), "no shape takes a partial step"
+
+
 # ------------------------------------------------------------------ (h)
 def test_edges_steps_and_batches(dev):
     qp, refs = pc.session_reference("Problem", 5)
