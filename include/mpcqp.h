@@ -14,6 +14,8 @@
  *   mpcqp_solve_box  <- the per-step IPOPT call of session_4/main.py:115-116
  *                       (session4_sol.py:128-129) for an input box
  *                       (lbx/ubx, main.py:68-69,97-98).
+ *   mpcqp_solve_box_vjp <- the sensitivity of that call's plan (main.py:115-116
+ *                       reports lam_p = dJ/dx0 only): dL/d(H, f, lb, ub) from dL/dz.
  *   mpcqp_mpc_box    <- both of the above fused for the input-box OCP
  *                       (MPCController.solve end to end, one launch).
  *   mpcqp_mpc_qp     <- MPCController.solve end to end with the input box AND
@@ -148,6 +150,44 @@ int mpcqp_solve_box(int dtype, int batch, int n,
                     const void* H, int64_t strideH, const void* f, int64_t stridef,
                     const void* lb, int64_t strideLb, const void* ub, int64_t strideUb,
                     void* z, int32_t* status, int max_iter, double tol, void* stream);
+
+/*
+ * Adjoint (vector-Jacobian product) of mpcqp_solve_box at its optimum z: the
+ * sensitivity of the plan that MPCController.solve (session_4/main.py:115-116)
+ * returns, next to the lam_p = dJ/dx0 it already reports.  With gz = dL/dz,
+ * A the rows held at a bound (z_i == lb_i or z_i == ub_i, compared exactly:
+ * the solvers write active rows as the bound itself) and F the free rows:
+ *
+ *   d_F  = -H_FF^{-1} gz_F,   d_A = 0           gf  = dL/df = d
+ *   nu_A = gz_A + H_AF d_F,   nu_F = 0          glb_i = nu_i where z_i sits at
+ *                                               lb_i, gub_i = nu_i where it sits
+ *                                               at ub_i (lb_i == ub_i == z_i:
+ *                                               glb), every other entry 0
+ *   dL/dH (full, unsymmetrised) = d z'          gH packed lower: (i, j<i) holds
+ *                                               d_i z_j + d_j z_i, (i, i) d_i z_i
+ *
+ * A row at a bound with a zero multiplier counts as active: the result is the
+ * one-sided derivative on the side that keeps the row there.
+ * H packed lower (stride 0 = shared), z and gz batch*n dense, lb/ub as in
+ * mpcqp_solve_box (NULL = -inf/+inf, stride 0 = shared), status the forward's
+ * status array (NULL = every instance OPTIMAL).  Outputs gf, glb, gub (n per
+ * instance), gH (n(n+1)/2 per instance) and vstatus are per instance, dense,
+ * and each may be NULL; gradients of shared inputs are left to the caller to
+ * sum.  vstatus[b] is a bare MPCQP_STATUS_* code: the low byte of status[b]
+ * when that is not OPTIMAL (MAXITER included: a clipped iterate is no KKT
+ * point; this goes first because the forward wrote NaN into z), else NONFINITE
+ * if H, gz or z holds a NaN/Inf, else NOT_CONVEX on a non-positive pivot of
+ * H_FF, else OPTIMAL.  Whenever it is not OPTIMAL all gradients of that
+ * instance are exact zeros.  Four instances per wavefront, |F| sweeps and one
+ * product.  Limit: n <= 32 (MPCQP_ENOTSUP above, with the limit in
+ * mpcqp_last_error()); batch == 0 returns MPCQP_OK.
+ */
+int mpcqp_solve_box_vjp(int dtype, int batch, int n,
+                        const void* H, int64_t strideH, const void* z,
+                        const void* lb, int64_t strideLb, const void* ub, int64_t strideUb,
+                        const int32_t* status, const void* gz,
+                        void* gf, void* glb, void* gub, void* gH,
+                        int32_t* vstatus, void* stream);
 
 /*
  * Fused per-instance condense + input-box QP (the whole MPCController.solve of

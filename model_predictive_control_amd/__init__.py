@@ -19,10 +19,24 @@ Submodules:
   bicycle        kinematic bicycle, integrators, batched FE linearisation
   mpc            MPCController (session_4/main.py) on device
   distributed    batch sharding / gather across GPUs
+  autograd       solve_box_diff, mpc_box_diff: the box QP and the fused box-MPC
+                 step as torch.autograd functions (also exported here)
 """
 from . import _native  # noqa: F401
 
 __version__ = "0.1.0"
+
+__all__ = ["library_path", "solve_box_diff", "mpc_box_diff"]
+
+
+def __getattr__(name):
+    # the two autograd entry points, resolved on first use so that importing
+    # the package stays free of torch
+    if name in ("solve_box_diff", "mpc_box_diff"):
+        from . import autograd
+
+        return getattr(autograd, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def library_path() -> str:

@@ -57,6 +57,8 @@ SIGNATURES = {
                             _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mpcqp_solve_box": (_i, [_i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                              _vp, _vp, _i, _d, _vp]),
+    "mpcqp_solve_box_vjp": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp,
+                                 _vp, _vp, _vp, _vp, _vp, _vp]),
     "mpcqp_mpc_box": (_i, [_i, _i, _i, _i, _i, _i,
                            _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                            _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i, _d, _vp]),

@@ -24,7 +24,7 @@ import torch
 from . import _native as nat
 
 __all__ = [
-    "condense", "solve_box", "mpc_box", "mpc_box_loop", "mpc_poly_loop", "tracking_terms", "mpc_qp", "mpc_ipm", "solve_poly", "solve_qp", "sweep", "riccati", "gemv",
+    "condense", "solve_box", "solve_box_vjp", "mpc_box", "mpc_box_loop", "mpc_poly_loop", "tracking_terms", "mpc_qp", "mpc_ipm", "solve_poly", "solve_qp", "sweep", "riccati", "gemv",
     "rollout", "bicycle_rti", "bicycle_linearise", "bicycle_hessian", "bicycle_sqp_step",
     "pack_lower", "unpack_lower", "status_code", "status_iters", "workspace_bytes",
 ]
@@ -517,6 +517,66 @@ def solve_box(H, f, lb=None, ub=None, *, max_iter: int = 0, tol: float = 0.0,
                                 _ptr(ws), wsb, _stream())
     nat.check(rc, "mpcqp_solve_box_ws")
     return z, status
+
+
+BOX_VJP_MAX_N = 32
+
+
+def solve_box_vjp(H, z, lb, ub, gz, *, status=None, need_H: bool = True) -> dict:
+    """Adjoint of ``solve_box`` at its optimum ``z`` (include/mpcqp.h
+    ``mpcqp_solve_box_vjp``): from ``gz = dL/dz`` (b, n) the gradients
+
+    * ``gf``  = d, with d_F = -H_FF^-1 gz_F on the free rows and 0 on the rows
+      at a bound (compared exactly);
+    * ``glb`` / ``gub`` = nu = gz_A + H_AF d_F on the side the row sits at;
+    * ``gH`` (packed lower, only with ``need_H``; else None): d z' folded onto
+      the packed entries, (i, j<i) = d_i z_j + d_j z_i, (i, i) = d_i z_i;
+    * ``vstatus`` (b,) int32: a bare status code; where it is not OPTIMAL every
+      gradient of the instance is exactly zero.
+
+    H, lb, ub as in ``solve_box`` (shared without a batch dimension, scalar or
+    None bounds); ``status`` is the forward's status (None = all optimal).  The
+    gradient of a shared H, lb or ub is summed over the batch and has the
+    shared shape.  A row at a bound with a zero multiplier counts as active
+    (one-sided derivative).  n <= 32."""
+    dt, dev = z.dtype, z.device
+    z = _dev(z, dt, dev)
+    gz = _dev(gz, dt, dev)
+    H = _dev(H, dt, dev)
+    if z.ndim != 2 or gz.shape != z.shape:
+        raise ValueError(f"z and gz must both be (batch, n), got {tuple(z.shape)} and {tuple(gz.shape)}")
+    batch, n = int(z.shape[0]), int(z.shape[1])
+    if H.shape[-1] != n * (n + 1) // 2:
+        raise ValueError(f"H must be packed lower with {n * (n + 1) // 2} entries, got {tuple(H.shape)}")
+    sH, bH = _inst(H, 1, "H")
+    lbt, slb = _bound(lb, n, dt, dev)
+    ubt, sub = _bound(ub, n, dt, dev)
+    for name, t in (("lb", lbt), ("ub", ubt)):
+        if t is not None and t.shape[-1] != n:
+            raise ValueError(f"{name}: last dimension {t.shape[-1]} != n = {n}")
+    _batch_of((1, batch), (sH, bH),
+              (slb, lbt.shape[0] if lbt is not None and lbt.ndim == 2 else None),
+              (sub, ubt.shape[0] if ubt is not None and ubt.ndim == 2 else None))
+    if status is not None:
+        if status.dtype != torch.int32 or status.shape != (batch,) or status.device != dev:
+            raise ValueError("status must be the forward's (batch,) int32 device tensor")
+        status = status.contiguous()
+    gf = torch.empty((batch, n), dtype=dt, device=dev)
+    glb = torch.empty((batch, n), dtype=dt, device=dev)
+    gub = torch.empty((batch, n), dtype=dt, device=dev)
+    gH = torch.empty((batch, n * (n + 1) // 2), dtype=dt, device=dev) if need_H else None
+    vstatus = torch.empty((batch,), dtype=torch.int32, device=dev)
+    rc = _lib().mpcqp_solve_box_vjp(_code(dt), batch, n, _ptr(H), sH, _ptr(z), _ptr(lbt), slb,
+                                    _ptr(ubt), sub, _ptr(status), _ptr(gz), _ptr(gf), _ptr(glb),
+                                    _ptr(gub), _ptr(gH), _ptr(vstatus), _stream())
+    nat.check(rc, "mpcqp_solve_box_vjp")
+    if gH is not None and sH == 0:
+        gH = gH.sum(0)
+    if slb == 0:
+        glb = glb.sum(0)
+    if sub == 0:
+        gub = gub.sum(0)
+    return {"gf": gf, "glb": glb, "gub": gub, "gH": gH, "vstatus": vstatus}
 
 
 # ------------------------------------------------------------- polytope QP

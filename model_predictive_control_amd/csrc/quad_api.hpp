@@ -38,6 +38,24 @@ struct MpcArgsQ {
   T tol;
 };
 
+// box_vjp.hip: the adjoint of the box QP at its optimum z (n <= 32); every
+// output and status / vstatus may be NULL
+template <typename T>
+struct BoxVjpArgs {
+  int batch, n;
+  const T* H; int64_t sH;
+  const T* z;
+  const T* lb; int64_t slb;
+  const T* ub; int64_t sub;
+  const int32_t* status;
+  const T* gz;
+  T *gf, *glb, *gub, *gH;
+  int32_t* vstatus;
+};
+constexpr int kBoxVjpMaxN = 32;
+template <typename T>
+int solve_box_vjp_quad(const BoxVjpArgs<T>& a, hipStream_t st);
+
 template <typename T>
 int solve_box_quad(const BoxArgsQ<T>& a, hipStream_t st);
 template <typename T>
