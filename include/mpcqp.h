@@ -16,6 +16,8 @@
  *                       (lbx/ubx, main.py:68-69,97-98).
  *   mpcqp_solve_box_vjp <- the sensitivity of that call's plan (main.py:115-116
  *                       reports lam_p = dJ/dx0 only): dL/d(H, f, lb, ub) from dL/dz.
+ *                       mpcqp_mpc_box_loop_vjp is the same through a whole
+ *                       closed-loop episode (simulate(...), main.py:270-271).
  *   mpcqp_mpc_box    <- both of the above fused for the input-box OCP
  *                       (MPCController.solve end to end, one launch).
  *   mpcqp_mpc_qp     <- MPCController.solve end to end with the input box AND
@@ -656,6 +658,69 @@ int mpcqp_mpc_box_loop_affine(int dtype, int batch, int nx, int nu, int N, int s
                               const void* g, int64_t strideG, const void* w,
                               void* xs, void* us, void* zs, int32_t* status, int max_iter,
                               double tol, void* stream);
+
+/*
+ * Adjoint (vector-Jacobian product) of mpcqp_mpc_box_loop[_affine]: the
+ * gradient of a loss L(xs, us, zs) of a whole closed-loop episode with respect
+ * to everything the loop takes, in one launch.  It replaces, per step of the
+ * episode in reverse, one mpcqp_solve_box_vjp (the sensitivity of the plan of
+ * MPCController.solve, session_4/main.py:115-116) plus the host algebra that
+ * carries the adjoint of the state through LinearSystem.simulate
+ * (session_1/LinearSystem.py:20-26) and simulate(...) (main.py:270-271).
+ * With the forward  f_t = F x_t + g_t,  z_t = argmin 1/2 z'Hz + f_t'z over the
+ * box,  u_t = z_t[0..nu),  x_{t+1} = A x_t + B u_t + w_t  and the upstream
+ * gradients gxs (dL/dxs, (steps+1) x batch x nx), gus (dL/dus, steps x batch x
+ * nu), gzs (dL/dzs, steps x batch x n), each of which may be NULL (= 0):
+ *
+ *   lam <- gxs[steps]
+ *   for t = steps-1 .. 0:
+ *     gz <- gzs[t];  gz[0..nu) += gus[t] + B'lam
+ *     A_t = rows with z_t,i == lb_i or z_t,i == ub_i (compared exactly), F_t the rest
+ *     d_F = -H_FF^{-1} gz_F, d_A = 0;  nu_A = gz_A + H_AF d_F, nu_F = 0
+ *                                       (the step of mpcqp_solve_box_vjp)
+ *     gg[t] = d   (dL/dg_t)             gw[t] = lam   (dL/dw_t; lam is lam_{t+1})
+ *     gH += d z_t' folded as in mpcqp_solve_box_vjp: packed (i, j<i) holds
+ *           d_i z_j + d_j z_i, (i, i) holds d_i z_i
+ *     gF += d x_t'   gA += lam x_t'   gB += lam u_t'
+ *     glb += nu where z_t sits at lb (lb == ub == z counts as lb), gub += nu at ub
+ *     lam <- gxs[t] + A'lam + F'd
+ *   gx0 = lam
+ *
+ * A row at a bound with a zero multiplier counts as active (the one-sided
+ * derivative that keeps it there), as in mpcqp_solve_box_vjp.
+ * H, F, A, Bm, lb, ub: as given to the forward (stride 0 = shared, lb/ub NULL
+ * = -inf/+inf).  xs ((steps+1) x batch x nx), zs (steps x batch x n) and status
+ * (steps x batch, NULL = every step OPTIMAL) are the forward's outputs; xs and
+ * zs are required when steps > 0.  Outputs, per instance and dense, each may
+ * be NULL: gx0 (nx), gH (n(n+1)/2), gF (n x nx), gA (nx x nx), gB (nx x nu),
+ * glb, gub (n), gg (steps x batch x n), gw (steps x batch x nx), vstatus
+ * (batch).  Gradients of shared inputs are left to the caller to sum.
+ * vstatus[b] is a bare MPCQP_STATUS_* code: the low byte of the first step's
+ * status that is not OPTIMAL (MAXITER included); else NONFINITE if H, F, A, Bm,
+ * a row t < steps of xs or zs, or a given upstream gradient row holds a
+ * NaN/Inf; else NOT_CONVEX on a non-positive pivot of H_FF at any step; else
+ * OPTIMAL.  Whenever it is not OPTIMAL every output of that instance is an
+ * exact zero, its rows of gg and gw included; the other instances of the
+ * wavefront are not affected.  steps == 0 gives gx0 = gxs[0] and zeros.
+ * Four instances per wavefront; H, F, A, Bm, the bounds, lam and all
+ * accumulators stay on chip for the episode, each step rebuilds H swept on
+ * its free rows (|F_t| sweeps and one product, bit for bit the step of
+ * mpcqp_solve_box_vjp), and only the rows of step t cross HBM, loaded one
+ * step ahead.  No scratch; the call only enqueues on `stream` and allocates
+ * nothing.  Limits: nx <= 4, nu <= 2, N*nu <= 32 (MPCQP_EINVAL outside, as
+ * mpcqp_mpc_box_loop); batch == 0 returns MPCQP_OK.
+ * Not supported: gradients through the condensing recursion (A, B -> H, F:
+ * gA and gB are those of the simulated plant only), the polytope, soft and
+ * bicycle loops, second derivatives, sweeps carried from one step to the next.
+ */
+int mpcqp_mpc_box_loop_vjp(int dtype, int batch, int nx, int nu, int N, int steps,
+                           const void* H, int64_t strideH, const void* F, int64_t strideF,
+                           const void* A, int64_t strideA, const void* Bm, int64_t strideB,
+                           const void* lb, int64_t strideLb, const void* ub, int64_t strideUb,
+                           const void* xs, const void* zs, const int32_t* status,
+                           const void* gxs, const void* gus, const void* gzs,
+                           void* gx0, void* gH, void* gF, void* gA, void* gB, void* glb, void* gub,
+                           void* gg, void* gw, int32_t* vstatus, void* stream);
 
 /*
  * The receding-horizon loop of a linear MPC with row (state) constraints and

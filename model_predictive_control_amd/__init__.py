@@ -20,19 +20,22 @@ Submodules:
   mpc            MPCController (session_4/main.py) on device
   distributed    batch sharding / gather across GPUs
   autograd       solve_box_diff, mpc_box_diff: the box QP and the fused box-MPC
-                 step as torch.autograd functions (also exported here)
+                 step as torch.autograd functions; box_loop_diff,
+                 mpc_box_loop_diff: the one-launch box-MPC episode with a
+                 one-launch backward (all four also exported here)
 """
 from . import _native  # noqa: F401
 
 __version__ = "0.1.0"
 
-__all__ = ["library_path", "solve_box_diff", "mpc_box_diff"]
+_AUTOGRAD = ("solve_box_diff", "mpc_box_diff", "box_loop_diff", "mpc_box_loop_diff")
+__all__ = ["library_path", *_AUTOGRAD]
 
 
 def __getattr__(name):
-    # the two autograd entry points, resolved on first use so that importing
+    # the autograd entry points, resolved on first use so that importing
     # the package stays free of torch
-    if name in ("solve_box_diff", "mpc_box_diff"):
+    if name in _AUTOGRAD:
         from . import autograd
 
         return getattr(autograd, name)

@@ -94,6 +94,7 @@ SIGNATURES = {
     "mpcqp_mpc_box_loop": (_i, [_i] * 6 + [_vp, _i64] * 7 + [_vp] * 3 + [_vp, _i, _d, _vp]),
     "mpcqp_mpc_box_loop_affine": (_i, [_i] * 7 + [_vp, _i64] * 7 + [_vp, _i64, _vp] + [_vp] * 3 +
                                   [_vp, _i, _d, _vp]),
+    "mpcqp_mpc_box_loop_vjp": (_i, [_i] * 6 + [_vp, _i64] * 6 + [_vp] * 17),
     "mpcqp_mpc_poly_loop": (_i, [_i] * 9 + [_vp] * 5 + [_i64, _vp, _vp, _i64] + [_vp] * 8 +
                             [_i, _d, _vp]),
     "mpcqp_mpc_poly_loop_soft": (_i, [_i] * 9 + [_vp] * 5 + [_i64, _vp, _vp, _i64] + [_vp] * 11 +

@@ -14,6 +14,19 @@ A row at a bound with a zero multiplier counts as active, so there the result
 is the one-sided derivative that keeps the row at its bound.  An instance whose
 forward solve did not end OPTIMAL (or whose adjoint meets a NaN or a
 non-positive pivot) contributes exact zeros to every gradient.  n <= 32.
+
+``box_loop_diff`` and ``mpc_box_loop_diff`` are the same for a whole
+closed-loop episode: the forward is ``batched.mpc_box_loop`` (one launch), the
+backward one launch of ``batched.mpc_box_loop_vjp`` (include/mpcqp.h
+``mpcqp_mpc_box_loop_vjp``), the reverse-time recursion
+
+    lam <- gxs[T];  for t = T-1 .. 0:  gz = gzs[t] (+ gus[t] + B'lam on u_t),
+    d, nu as above at z_t,  dL/dg_t = d,  dL/dw_t = lam,  dL/dH += d z_t',
+    dL/dF += d x_t',  dL/dA += lam x_t',  dL/dB += lam u_t',
+    lam <- gxs[t] + A'lam + F'd;   dL/dx0 = lam
+
+with the same conventions; an instance with a step that did not end OPTIMAL
+contributes exact zeros.  nx <= 4, nu <= 2, n <= 32.
 """
 from __future__ import annotations
 
@@ -22,7 +35,7 @@ from torch.autograd.function import once_differentiable
 
 from . import batched
 
-__all__ = ["solve_box_diff", "mpc_box_diff"]
+__all__ = ["solve_box_diff", "mpc_box_diff", "box_loop_diff", "mpc_box_loop_diff"]
 
 MAX_N = batched.BOX_VJP_MAX_N
 
@@ -178,3 +191,111 @@ def mpc_box_diff(A, B, Q, R, Qf, N, x0, lb=None, ub=None, c=None, *, tv=False, *
         raise NotImplementedError(
             f"mpc_box_diff: gradients are limited to N * nu <= {MAX_N}, got {n}")
     return _MpcBox.apply(A, B, Q, R, Qf, x0, lb, ub, c, int(N), bool(tv), kw)
+
+
+class _BoxLoop(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, H, F, A, B, x0, lb, ub, g, w, steps, kw):
+        nu = int(B.shape[-1])
+        N = int(F.shape[-2]) // nu
+        o = batched.mpc_box_loop(A, B, None, None, None, N, x0, lb, ub, steps, plans=True,
+                                 condensed={"H": H, "F": F}, g=g, w=w, **kw)
+        xs, us, zs, status = o["xs"], o["us"], o["zs"], o["status"]
+        ctx.mark_non_differentiable(status)
+        ctx.set_materialize_grads(False)
+        opt = (lb, ub, g)
+        ctx.flags = [isinstance(t, torch.Tensor) for t in opt]
+        ctx.plain = [None if isinstance(t, torch.Tensor) else t for t in opt]
+        ctx.save_for_backward(H, F, A, B, xs, zs, status, *[t for t in opt if isinstance(t, torch.Tensor)])
+        return xs, us, zs, status
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gxs, gus, gzs, _gstatus):
+        saved = list(ctx.saved_tensors)
+        H, F, A, B, xs, zs, status = saved[:7]
+        rest = saved[7:]
+        lb, ub, g = (rest.pop(0) if fl else pl for fl, pl in zip(ctx.flags, ctx.plain))
+        need = ctx.needs_input_grad  # H, F, A, B, x0, lb, ub, g, w
+        names = ("gH", "gF", "gA", "gB", "gx0", "glb", "gub", "gg", "gw")
+        want = tuple(k for k, nd in zip(names, need) if nd)
+        dt = zs.dtype
+        r = batched.mpc_box_loop_vjp(H, F, A, B, lb, ub, xs, zs,
+                                     *(None if t is None else t.to(dt) for t in (gxs, gus, gzs)),
+                                     status=status, need=want)
+        glb = _like_input(r["glb"], lb) if ctx.flags[0] and need[5] else None
+        gub = _like_input(r["gub"], ub) if ctx.flags[1] and need[6] else None
+        gg = r["gg"]
+        if gg is not None and g.ndim == 2:  # shared by the batch
+            gg = gg.sum(1)
+        return r["gH"], r["gF"], r["gA"], r["gB"], r["gx0"], glb, gub, gg, r["gw"], None, None
+
+
+def box_loop_diff(H, F, A, B, x0, lb=None, ub=None, *, steps, g=None, w=None, cold=False,
+                  max_iter=0, tol=0.0):
+    """``batched.mpc_box_loop`` on a condensed problem (packed H, F: f_t = F x_t
+    + g_t) with gradients: returns ``(xs, us, zs, status)`` where xs (T+1, b,
+    nx), us (T, b, nu) and zs (T, b, n) carry the graph to H, F, the plant A, B
+    of the simulation, x0 (b, nx), tensor lb / ub, g ((T, n) shared: summed over
+    the batch, or (T, b, n)) and w (T, b, nx); status is non-differentiable.
+    The forward is ``mpc_box_loop(..., condensed={"H": H, "F": F}, plans=True)``
+    unchanged, the backward one launch of ``batched.mpc_box_loop_vjp``.  H and F
+    are independent inputs here: no gradient flows from them to A and B (the
+    condensing recursion is not differentiated)."""
+    kw = dict(cold=bool(cold), max_iter=int(max_iter), tol=float(tol))
+    return _BoxLoop.apply(H, F, A, B, x0, lb, ub, g, w, int(steps), kw)
+
+
+def mpc_box_loop_diff(A, B, Q, R, Qf, N, x0, lb=None, ub=None, *, steps, x_ref=None, u_ref=None,
+                      w=None, cold=False, max_iter=0, tol=0.0):
+    """``batched.mpc_box_loop`` (the one-launch input-box MPC episode, with
+    reference tracking and disturbances) with gradients: returns ``(xs, us, zs,
+    status)``, bit for bit the values of ``mpc_box_loop(..., plans=True)``,
+    where xs, us, zs carry the graph to the shared weights Q, R, Qf, to x0, to
+    tensor lb / ub, to w and to the references.  The plant is condensed once
+    (``batched.condense``); the graph to the weights is carried by torch
+    expressions on the detached Gam, Phi of that call,
+
+        H = Gam' Qhat Gam + Rhat,  F = Gam' Qhat Phi,  g = tracking_terms(...)
+
+    attached to the kernel's own H and F as value + (expr - expr.detach()), and
+    ``box_loop_diff`` does the rest.  Gradients of the weights are symmetric.
+    Gradients through A or B (the condensing recursion) are not provided; those
+    of the simulated plant alone are what ``box_loop_diff`` gives."""
+    if _needs(A, B):
+        raise NotImplementedError(
+            "mpc_box_loop_diff: gradients through A and B (the condensing recursion) are not "
+            "implemented; detach them, or use box_loop_diff for the simulated plant's")
+    N, T = int(N), int(steps)
+    nx, nu = int(B.shape[-2]), int(B.shape[-1])
+    tracking = x_ref is not None or u_ref is not None
+    dt, dev = A.dtype, A.device
+    wts = [torch.as_tensor(v, dtype=dt, device=dev) for v in (Q, R, Qf)]
+    Q, R, Qf = wts[0], batched._weight_r(wts[1], nu), wts[2]
+    if Q.ndim != 2 or R.ndim != 2 or Qf.ndim != 2:
+        raise NotImplementedError("mpc_box_loop_diff: Q, R, Qf must be shared by the batch")
+    det = [v.detach() for v in (Q, R, Qf)]
+    if _needs(Q, R, Qf):
+        # the value of each weight with the graph of its symmetric part
+        Q, R, Qf = (v.detach() + (_sym(v) - _sym(v).detach()) for v in (Q, R, Qf))
+    # the condensing call of mpc_box_loop itself (its H and F are the values)
+    cd = batched.condense(A, B, *det, N, outputs=("H", "F", "Gam") if tracking else ("H", "F"))
+    H, F = cd["H"], cd["F"]
+    g = None
+    if _needs(Q, R, Qf):
+        aux = batched.condense(A, B, *det, N, outputs=("Gam", "Phi"))
+        Gam, Phi = aux["Gam"], aux["Phi"]
+        Qhat = torch.block_diag(*([Q] * (N - 1) + [Qf]))
+        Rhat = torch.block_diag(*([R] * N))
+        GQ = Gam.transpose(-1, -2) @ Qhat
+        He = batched.pack_lower(GQ @ Gam + Rhat)
+        Fe = GQ @ Phi
+        H = H + (He - He.detach())
+        F = F + (Fe - Fe.detach())
+    if tracking:
+        Gam = cd["Gam"]
+        if Gam.ndim == 3 and Gam.shape[0] == 1:
+            Gam = Gam[0]
+        g = batched.tracking_terms({"Gam": Gam}, Q, R, Qf, N, T, x_ref, u_ref)
+    return box_loop_diff(H, F, A, B, x0, lb, ub, steps=T, g=g, w=w, cold=cold, max_iter=max_iter,
+                         tol=tol)

@@ -24,7 +24,7 @@ import torch
 from . import _native as nat
 
 __all__ = [
-    "condense", "solve_box", "solve_box_vjp", "mpc_box", "mpc_box_loop", "mpc_poly_loop", "tracking_terms", "mpc_qp", "mpc_ipm", "solve_poly", "solve_qp", "sweep", "riccati", "gemv",
+    "condense", "solve_box", "solve_box_vjp", "mpc_box", "mpc_box_loop", "mpc_box_loop_vjp", "mpc_poly_loop", "tracking_terms", "mpc_qp", "mpc_ipm", "solve_poly", "solve_qp", "sweep", "riccati", "gemv",
     "rollout", "bicycle_rti", "bicycle_linearise", "bicycle_hessian", "bicycle_sqp_step",
     "pack_lower", "unpack_lower", "status_code", "status_iters", "workspace_bytes",
 ]
@@ -577,6 +577,98 @@ def solve_box_vjp(H, z, lb, ub, gz, *, status=None, need_H: bool = True) -> dict
     if sub == 0:
         gub = gub.sum(0)
     return {"gf": gf, "glb": glb, "gub": gub, "gH": gH, "vstatus": vstatus}
+
+
+LOOP_VJP_OUTPUTS = ("gx0", "gH", "gF", "gA", "gB", "glb", "gub", "gg", "gw")
+
+
+def mpc_box_loop_vjp(H, F, A, B, lb, ub, xs, zs, gxs=None, gus=None, gzs=None, *, status=None,
+                     need=LOOP_VJP_OUTPUTS) -> dict:
+    """Adjoint of ``mpc_box_loop`` over the whole episode, one launch
+    (include/mpcqp.h ``mpcqp_mpc_box_loop_vjp``).  ``xs`` (T+1, b, nx), ``zs``
+    (T, b, n) and ``status`` (T, b; None = every step optimal) are the
+    forward's outputs; H (packed), F, A, B, lb, ub its inputs (shared without a
+    batch dimension, or per instance; a leading dimension of 1 counts as
+    shared).  ``gxs`` (T+1, b, nx), ``gus`` (T, b, nu), ``gzs`` (T, b, n) are
+    dL/dxs, dL/dus, dL/dzs; None means zero.  Returns a dict with the entries of
+    ``need`` (the others None) out of
+
+    * ``gx0`` (b, nx); ``gg`` (T, b, n) = dL/dg_t; ``gw`` (T, b, nx) = dL/dw_t;
+    * ``gH`` (packed, folded as in ``solve_box_vjp``), ``gF``, ``gA``, ``gB``,
+      ``glb``, ``gub``: in the shape of the input, summed over the batch where
+      the input is shared;
+
+    and ``vstatus`` (b,) int32, a bare status code: where it is not OPTIMAL
+    every gradient of the instance is exactly zero.  Limits of the loop: nx <=
+    4, nu <= 2, n <= 32."""
+    dt, dev = xs.dtype, xs.device
+    xs, zs = _dev(xs, dt, dev), _dev(zs, dt, dev)
+    H, F, A, B = _dev(H, dt, dev), _dev(F, dt, dev), _dev(A, dt, dev), _dev(B, dt, dev)
+    if xs.ndim != 3 or zs.ndim != 3 or xs.shape[0] != zs.shape[0] + 1 or xs.shape[1] != zs.shape[1]:
+        raise ValueError(f"xs must be (T+1, b, nx) and zs (T, b, n), got {tuple(xs.shape)} and "
+                         f"{tuple(zs.shape)}")
+    T, batch, n = (int(v) for v in zs.shape)
+    nx, nu = int(B.shape[-2]), int(B.shape[-1])
+    if xs.shape[2] != nx or n % nu or H.shape[-1] != n * (n + 1) // 2 \
+            or tuple(F.shape[-2:]) != (n, nx) or tuple(A.shape[-2:]) != (nx, nx):
+        raise ValueError(f"inconsistent shapes: H {tuple(H.shape)}, F {tuple(F.shape)}, A "
+                         f"{tuple(A.shape)}, B {tuple(B.shape)}, xs {tuple(xs.shape)}, zs "
+                         f"{tuple(zs.shape)}")
+    unknown = set(need) - set(LOOP_VJP_OUTPUTS)
+    if unknown:
+        raise ValueError(f"need: unknown outputs {sorted(unknown)}")
+
+    def inst(t, base, name):
+        s, bt = _inst(t, base, name)
+        if bt == 1 and batch > 1:   # a shared plant condenses to one instance
+            s, bt = 0, None
+        return s, bt
+
+    sH, bH = inst(H, 1, "H")
+    sF, bF = inst(F, 2, "F")
+    sA, bA = inst(A, 2, "A")
+    sB, bB = inst(B, 2, "B")
+    lbt, slb = _bound(lb, n, dt, dev)
+    ubt, sub = _bound(ub, n, dt, dev)
+    for name, t in (("lb", lbt), ("ub", ubt)):
+        if t is not None and t.shape[-1] != n:
+            raise ValueError(f"{name}: last dimension {t.shape[-1]} != n = {n}")
+    _batch_of((1, batch), (sH, bH), (sF, bF), (sA, bA), (sB, bB),
+              (slb, lbt.shape[0] if lbt is not None and lbt.ndim == 2 else None),
+              (sub, ubt.shape[0] if ubt is not None and ubt.ndim == 2 else None))
+    ups = {}
+    for name, t, shp in (("gxs", gxs, (T + 1, batch, nx)), ("gus", gus, (T, batch, nu)),
+                         ("gzs", gzs, (T, batch, n))):
+        t = _dev(t, dt, dev)
+        if t is not None and tuple(t.shape) != shp:
+            raise ValueError(f"{name} must be {shp}, got {tuple(t.shape)}")
+        ups[name] = t
+    if status is not None:
+        if status.dtype != torch.int32 or tuple(status.shape) != (T, batch) or status.device != dev:
+            raise ValueError("status must be the forward's (T, batch) int32 device tensor")
+        status = status.contiguous()
+    shapes = dict(gx0=(batch, nx), gH=(batch, n * (n + 1) // 2), gF=(batch, n, nx),
+                  gA=(batch, nx, nx), gB=(batch, nx, nu), glb=(batch, n), gub=(batch, n),
+                  gg=(T, batch, n), gw=(T, batch, nx))
+    o = {k: (torch.empty(shapes[k], dtype=dt, device=dev) if k in need else None)
+         for k in LOOP_VJP_OUTPUTS}
+    vstatus = torch.empty((batch,), dtype=torch.int32, device=dev)
+    rc = _lib().mpcqp_mpc_box_loop_vjp(
+        _code(dt), batch, nx, nu, n // nu, T, _ptr(H), sH, _ptr(F), sF, _ptr(A), sA, _ptr(B), sB,
+        _ptr(lbt), slb, _ptr(ubt), sub, _ptr(xs), _ptr(zs), _ptr(status), _ptr(ups["gxs"]),
+        _ptr(ups["gus"]), _ptr(ups["gzs"]), *(_ptr(o[k]) for k in LOOP_VJP_OUTPUTS),
+        _ptr(vstatus), _stream())
+    nat.check(rc, "mpcqp_mpc_box_loop_vjp")
+    # gradients of shared inputs: summed over the batch, in the input's shape
+    for k, s, ref in (("gH", sH, H), ("gF", sF, F), ("gA", sA, A), ("gB", sB, B)):
+        if o[k] is not None and s == 0:
+            o[k] = o[k].sum(0).reshape(ref.shape)
+    if o["glb"] is not None and slb == 0:
+        o["glb"] = o["glb"].sum(0)
+    if o["gub"] is not None and sub == 0:
+        o["gub"] = o["gub"].sum(0)
+    o["vstatus"] = vstatus
+    return o
 
 
 # ------------------------------------------------------------- polytope QP

@@ -25,10 +25,10 @@
 // outcome is not OPTIMAL gets exact zeros in every gradient (a NaN would
 // poison the batch sum of a shared parameter's gradient); the caller has
 // vstatus.  Division is IEEE: the pivot reciprocal is a plain division
-// (sweep_col_ieee below) and the file is built without the approximate-division
-// flags.
-#include "quad.hpp"
+// (sweep_col_ieee, sweep_ieee.hpp) and the file is built without the
+// approximate-division flags.
 #include "quad_api.hpp"
+#include "sweep_ieee.hpp"
 
 namespace mpcqp {
 
@@ -47,35 +47,6 @@ struct VjpLds {
   static constexpr int oP = oD + NMAX;
   static constexpr int size = (oP + PMAX + 1) & ~1;
 };
-
-// QSym::sweep_col (sigma = +1) with the pivot's reciprocal from an IEEE
-// division instead of fast_rcp: a group sweeps |F| rows once, so the division
-// is not on a long serial chain here.  Same selects as the layout's own sweep:
-// row and column k are set, not produced by cancellation.
-template <typename T, int BS>
-__device__ __forceinline__ void sweep_col_ieee(QSym<T, BS>& M, int k, T d, const T (&colr)[BS],
-                                               const T (&colc)[BS]) {
-  const T rd = T(1) / d;
-  T a[BS], srow[BS];
-  bool ik[BS], jk[BS];
-#pragma unroll
-  for (int r = 0; r < BS; ++r) {
-    a[r] = colr[r] * rd;
-    ik[r] = (M.bi * BS + r == k);
-  }
-#pragma unroll
-  for (int c = 0; c < BS; ++c) {
-    jk[c] = (M.bj * BS + c == k);
-    srow[c] = jk[c] ? -rd : colc[c] * rd;
-  }
-#pragma unroll
-  for (int r = 0; r < BS; ++r)
-#pragma unroll
-    for (int c = 0; c < BS; ++c) {
-      const T gen = fma(-a[r], colc[c], M.m[r][c]);
-      M.m[r][c] = ik[r] ? srow[c] : (jk[c] ? a[r] : gen);
-    }
-}
 
 template <typename T, int BS>
 __global__ __launch_bounds__(64) void box_vjp_quad_kernel(BoxVjpArgs<T> a) {
