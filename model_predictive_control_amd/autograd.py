@@ -52,40 +52,46 @@ def _like_input(g, ref):
     return g.reshape(ref.shape)
 
 
+def _stash(ctx, tensors, optional):
+    """Save for backward: ``tensors``, and of the optional inputs those that
+    are tensors; anything else among them (None, a Python scalar) stays on
+    ``ctx``."""
+    ctx.opt_plain = [None if isinstance(t, torch.Tensor) else t for t in optional]
+    ctx.opt_tensor = [isinstance(t, torch.Tensor) for t in optional]
+    ctx.save_for_backward(*tensors, *(t for t in optional if isinstance(t, torch.Tensor)))
+
+
+def _recover(ctx, k):
+    """The ``k`` tensors and the optional inputs of ``_stash``, in its order."""
+    saved = list(ctx.saved_tensors)
+    rest = saved[k:]
+    return saved[:k] + [rest.pop(0) if fl else pl for fl, pl in zip(ctx.opt_tensor, ctx.opt_plain)]
+
+
+def _bound_grad(g, bound, needed):
+    """The gradient of a bound given as a tensor, in its shape; None otherwise."""
+    return _like_input(g, bound) if isinstance(bound, torch.Tensor) and needed else None
+
+
 class _SolveBox(torch.autograd.Function):
     @staticmethod
     def forward(ctx, H, f, lb, ub, kw):
         z, status = batched.solve_box(H, f, lb, ub, **kw)
         ctx.mark_non_differentiable(status)
-        tens = [H, f, z, status]
-        ctx.lb_t = isinstance(lb, torch.Tensor)
-        ctx.ub_t = isinstance(ub, torch.Tensor)
-        ctx.lb = None if ctx.lb_t else lb
-        ctx.ub = None if ctx.ub_t else ub
-        if ctx.lb_t:
-            tens.append(lb)
-        if ctx.ub_t:
-            tens.append(ub)
-        ctx.save_for_backward(*tens)
+        _stash(ctx, (H, f, z, status), (lb, ub))
         return z, status
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gz, _gstatus):
-        saved = list(ctx.saved_tensors)
-        H, f, z, status = saved[:4]
-        rest = saved[4:]
-        lb = rest.pop(0) if ctx.lb_t else ctx.lb
-        ub = rest.pop(0) if ctx.ub_t else ctx.ub
+        H, f, z, status, lb, ub = _recover(ctx, 4)
         need = ctx.needs_input_grad
         r = batched.solve_box_vjp(H, z, lb, ub, gz.to(z.dtype), status=status, need_H=need[0])
         gH = r["gH"] if need[0] else None
         gf = None
         if need[1]:
             gf = r["gf"] if f.ndim == 2 else r["gf"].sum(0)
-        glb = _like_input(r["glb"], lb) if ctx.lb_t and need[2] else None
-        gub = _like_input(r["gub"], ub) if ctx.ub_t and need[3] else None
-        return gH, gf, glb, gub, None
+        return gH, gf, _bound_grad(r["glb"], lb, need[2]), _bound_grad(r["gub"], ub, need[3]), None
 
 
 def solve_box_diff(H, f, lb=None, ub=None, **kw):
@@ -109,21 +115,14 @@ class _MpcBox(torch.autograd.Function):
     def forward(ctx, A, B, Q, R, Qf, x0, lb, ub, c, N, tv, kw):
         z, status = batched.mpc_box(A, B, Q, R, Qf, N, x0, lb, ub, c, tv=tv, **kw)
         ctx.mark_non_differentiable(status)
-        tens = [A, B, Q, R, Qf, x0, z, status]
-        ctx.flags = [isinstance(t, torch.Tensor) for t in (lb, ub, c)]
-        ctx.plain = [None if isinstance(t, torch.Tensor) else t for t in (lb, ub, c)]
-        tens += [t for t in (lb, ub, c) if isinstance(t, torch.Tensor)]
-        ctx.save_for_backward(*tens)
+        _stash(ctx, (A, B, Q, R, Qf, x0, z, status), (lb, ub, c))
         ctx.N, ctx.tv = N, tv
         return z, status
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gz, _gstatus):
-        saved = list(ctx.saved_tensors)
-        A, B, Q, R, Qf, x0, z, status = saved[:8]
-        rest = saved[8:]
-        lb, ub, c = (rest.pop(0) if fl else pl for fl, pl in zip(ctx.flags, ctx.plain))
+        A, B, Q, R, Qf, x0, z, status, lb, ub, c = _recover(ctx, 8)
         need = ctx.needs_input_grad
         N = ctx.N
         nx, nu = int(B.shape[-2]), int(B.shape[-1])
@@ -168,8 +167,7 @@ class _MpcBox(torch.autograd.Function):
             if R.ndim <= 2:
                 gR = gR.sum(0)
             gR = gR.reshape(R.shape)
-        glb = _like_input(r["glb"], lb) if ctx.flags[0] and need[6] else None
-        gub = _like_input(r["gub"], ub) if ctx.flags[1] and need[7] else None
+        glb, gub = _bound_grad(r["glb"], lb, need[6]), _bound_grad(r["gub"], ub, need[7])
         return None, None, gQ, gR, gQf, gx0, glb, gub, None, None, None, None
 
 
@@ -203,19 +201,13 @@ class _BoxLoop(torch.autograd.Function):
         xs, us, zs, status = o["xs"], o["us"], o["zs"], o["status"]
         ctx.mark_non_differentiable(status)
         ctx.set_materialize_grads(False)
-        opt = (lb, ub, g)
-        ctx.flags = [isinstance(t, torch.Tensor) for t in opt]
-        ctx.plain = [None if isinstance(t, torch.Tensor) else t for t in opt]
-        ctx.save_for_backward(H, F, A, B, xs, zs, status, *[t for t in opt if isinstance(t, torch.Tensor)])
+        _stash(ctx, (H, F, A, B, xs, zs, status), (lb, ub, g))
         return xs, us, zs, status
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gxs, gus, gzs, _gstatus):
-        saved = list(ctx.saved_tensors)
-        H, F, A, B, xs, zs, status = saved[:7]
-        rest = saved[7:]
-        lb, ub, g = (rest.pop(0) if fl else pl for fl, pl in zip(ctx.flags, ctx.plain))
+        H, F, A, B, xs, zs, status, lb, ub, g = _recover(ctx, 7)
         need = ctx.needs_input_grad  # H, F, A, B, x0, lb, ub, g, w
         names = ("gH", "gF", "gA", "gB", "gx0", "glb", "gub", "gg", "gw")
         want = tuple(k for k, nd in zip(names, need) if nd)
@@ -223,8 +215,7 @@ class _BoxLoop(torch.autograd.Function):
         r = batched.mpc_box_loop_vjp(H, F, A, B, lb, ub, xs, zs,
                                      *(None if t is None else t.to(dt) for t in (gxs, gus, gzs)),
                                      status=status, need=want)
-        glb = _like_input(r["glb"], lb) if ctx.flags[0] and need[5] else None
-        gub = _like_input(r["gub"], ub) if ctx.flags[1] and need[6] else None
+        glb, gub = _bound_grad(r["glb"], lb, need[5]), _bound_grad(r["gub"], ub, need[6])
         gg = r["gg"]
         if gg is not None and g.ndim == 2:  # shared by the batch
             gg = gg.sum(1)

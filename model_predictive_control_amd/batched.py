@@ -522,6 +522,36 @@ def solve_box(H, f, lb=None, ub=None, *, max_iter: int = 0, tol: float = 0.0,
 BOX_VJP_MAX_N = 32
 
 
+def _vjp_common(lb, ub, n, dt, dev, batch, insts, status, status_shape):
+    """What ``solve_box_vjp`` and ``mpc_box_loop_vjp`` share around their
+    launch: the bounds (``_bound``, last dimension n), the batch consistency of
+    ``insts`` ((stride, batch) pairs) and the bounds with ``batch``, and the
+    forward's status.  Returns ``(lbt, slb, ubt, sub, status, shared)`` where
+    ``shared(g, stride, ref=None)`` is the epilogue of a gradient: summed over
+    the batch where the input is shared (stride 0), in the shape of ``ref``."""
+    lbt, slb = _bound(lb, n, dt, dev)
+    ubt, sub = _bound(ub, n, dt, dev)
+    for name, t in (("lb", lbt), ("ub", ubt)):
+        if t is not None and t.shape[-1] != n:
+            raise ValueError(f"{name}: last dimension {t.shape[-1]} != n = {n}")
+    _batch_of((1, batch), *insts,
+              (slb, lbt.shape[0] if lbt is not None and lbt.ndim == 2 else None),
+              (sub, ubt.shape[0] if ubt is not None and ubt.ndim == 2 else None))
+    if status is not None:
+        if status.dtype != torch.int32 or tuple(status.shape) != status_shape or status.device != dev:
+            what = "(batch,)" if len(status_shape) == 1 else "(T, batch)"
+            raise ValueError(f"status must be the forward's {what} int32 device tensor")
+        status = status.contiguous()
+
+    def shared(g, stride, ref=None):
+        if g is None or stride != 0:
+            return g
+        g = g.sum(0)
+        return g if ref is None else g.reshape(ref.shape)
+
+    return lbt, slb, ubt, sub, status, shared
+
+
 def solve_box_vjp(H, z, lb, ub, gz, *, status=None, need_H: bool = True) -> dict:
     """Adjoint of ``solve_box`` at its optimum ``z`` (include/mpcqp.h
     ``mpcqp_solve_box_vjp``): from ``gz = dL/dz`` (b, n) the gradients
@@ -549,18 +579,8 @@ def solve_box_vjp(H, z, lb, ub, gz, *, status=None, need_H: bool = True) -> dict
     if H.shape[-1] != n * (n + 1) // 2:
         raise ValueError(f"H must be packed lower with {n * (n + 1) // 2} entries, got {tuple(H.shape)}")
     sH, bH = _inst(H, 1, "H")
-    lbt, slb = _bound(lb, n, dt, dev)
-    ubt, sub = _bound(ub, n, dt, dev)
-    for name, t in (("lb", lbt), ("ub", ubt)):
-        if t is not None and t.shape[-1] != n:
-            raise ValueError(f"{name}: last dimension {t.shape[-1]} != n = {n}")
-    _batch_of((1, batch), (sH, bH),
-              (slb, lbt.shape[0] if lbt is not None and lbt.ndim == 2 else None),
-              (sub, ubt.shape[0] if ubt is not None and ubt.ndim == 2 else None))
-    if status is not None:
-        if status.dtype != torch.int32 or status.shape != (batch,) or status.device != dev:
-            raise ValueError("status must be the forward's (batch,) int32 device tensor")
-        status = status.contiguous()
+    lbt, slb, ubt, sub, status, shared = _vjp_common(lb, ub, n, dt, dev, batch, [(sH, bH)],
+                                                     status, (batch,))
     gf = torch.empty((batch, n), dtype=dt, device=dev)
     glb = torch.empty((batch, n), dtype=dt, device=dev)
     gub = torch.empty((batch, n), dtype=dt, device=dev)
@@ -570,13 +590,8 @@ def solve_box_vjp(H, z, lb, ub, gz, *, status=None, need_H: bool = True) -> dict
                                     _ptr(ubt), sub, _ptr(status), _ptr(gz), _ptr(gf), _ptr(glb),
                                     _ptr(gub), _ptr(gH), _ptr(vstatus), _stream())
     nat.check(rc, "mpcqp_solve_box_vjp")
-    if gH is not None and sH == 0:
-        gH = gH.sum(0)
-    if slb == 0:
-        glb = glb.sum(0)
-    if sub == 0:
-        gub = gub.sum(0)
-    return {"gf": gf, "glb": glb, "gub": gub, "gH": gH, "vstatus": vstatus}
+    return {"gf": gf, "glb": shared(glb, slb), "gub": shared(gub, sub), "gH": shared(gH, sH),
+            "vstatus": vstatus}
 
 
 LOOP_VJP_OUTPUTS = ("gx0", "gH", "gF", "gA", "gB", "glb", "gub", "gg", "gw")
@@ -628,14 +643,8 @@ def mpc_box_loop_vjp(H, F, A, B, lb, ub, xs, zs, gxs=None, gus=None, gzs=None, *
     sF, bF = inst(F, 2, "F")
     sA, bA = inst(A, 2, "A")
     sB, bB = inst(B, 2, "B")
-    lbt, slb = _bound(lb, n, dt, dev)
-    ubt, sub = _bound(ub, n, dt, dev)
-    for name, t in (("lb", lbt), ("ub", ubt)):
-        if t is not None and t.shape[-1] != n:
-            raise ValueError(f"{name}: last dimension {t.shape[-1]} != n = {n}")
-    _batch_of((1, batch), (sH, bH), (sF, bF), (sA, bA), (sB, bB),
-              (slb, lbt.shape[0] if lbt is not None and lbt.ndim == 2 else None),
-              (sub, ubt.shape[0] if ubt is not None and ubt.ndim == 2 else None))
+    lbt, slb, ubt, sub, status, shared = _vjp_common(
+        lb, ub, n, dt, dev, batch, [(sH, bH), (sF, bF), (sA, bA), (sB, bB)], status, (T, batch))
     ups = {}
     for name, t, shp in (("gxs", gxs, (T + 1, batch, nx)), ("gus", gus, (T, batch, nu)),
                          ("gzs", gzs, (T, batch, n))):
@@ -643,10 +652,6 @@ def mpc_box_loop_vjp(H, F, A, B, lb, ub, xs, zs, gxs=None, gus=None, gzs=None, *
         if t is not None and tuple(t.shape) != shp:
             raise ValueError(f"{name} must be {shp}, got {tuple(t.shape)}")
         ups[name] = t
-    if status is not None:
-        if status.dtype != torch.int32 or tuple(status.shape) != (T, batch) or status.device != dev:
-            raise ValueError("status must be the forward's (T, batch) int32 device tensor")
-        status = status.contiguous()
     shapes = dict(gx0=(batch, nx), gH=(batch, n * (n + 1) // 2), gF=(batch, n, nx),
                   gA=(batch, nx, nx), gB=(batch, nx, nu), glb=(batch, n), gub=(batch, n),
                   gg=(T, batch, n), gw=(T, batch, nx))
@@ -659,14 +664,9 @@ def mpc_box_loop_vjp(H, F, A, B, lb, ub, xs, zs, gxs=None, gus=None, gzs=None, *
         _ptr(ups["gus"]), _ptr(ups["gzs"]), *(_ptr(o[k]) for k in LOOP_VJP_OUTPUTS),
         _ptr(vstatus), _stream())
     nat.check(rc, "mpcqp_mpc_box_loop_vjp")
-    # gradients of shared inputs: summed over the batch, in the input's shape
-    for k, s, ref in (("gH", sH, H), ("gF", sF, F), ("gA", sA, A), ("gB", sB, B)):
-        if o[k] is not None and s == 0:
-            o[k] = o[k].sum(0).reshape(ref.shape)
-    if o["glb"] is not None and slb == 0:
-        o["glb"] = o["glb"].sum(0)
-    if o["gub"] is not None and sub == 0:
-        o["gub"] = o["gub"].sum(0)
+    for k, s, ref in (("gH", sH, H), ("gF", sF, F), ("gA", sA, A), ("gB", sB, B),
+                      ("glb", slb, None), ("gub", sub, None)):
+        o[k] = shared(o[k], s, ref)
     o["vstatus"] = vstatus
     return o
 

@@ -15,22 +15,36 @@
 // M_AF = H_AF H_FF^{-1}, so one mat-vec out = M [g_F; 0] yields d_F = out_F and
 // nu_A = g_A - out_A: |F| sweeps and one product, no iterations.
 //
-// The four groups of a wave hold different free sets: the sweep loop runs
-// while any group has a row left, every group passes every LDS publish of
-// QSym::column, and a group with nothing left to sweep discards what it read
-// (the "H swept on the guessed free rows only" loop of loop_box.hip).
+// The step itself (row states, sweeps, product, d and nu) and the fold of d z'
+// are box_vjp_core.hpp, shared with loop_box_vjp.hip.
 //
 // A row at a bound with a zero multiplier counts as active: the result is the
 // one-sided derivative on the side that keeps it there.  An instance whose
 // outcome is not OPTIMAL gets exact zeros in every gradient (a NaN would
 // poison the batch sum of a shared parameter's gradient); the caller has
 // vstatus.  Division is IEEE: the pivot reciprocal is a plain division
-// (sweep_col_ieee, sweep_ieee.hpp) and the file is built without the
-// approximate-division flags.
+// (sweep_col_ieee) and the file is built without the approximate-division
+// flags.
+#include "box_vjp_core.hpp"
 #include "quad_api.hpp"
-#include "sweep_ieee.hpp"
 
 namespace mpcqp {
+
+constexpr int kBoxVjpMaxN = 32;
+
+// every output and status / vstatus may be null
+template <typename T>
+struct BoxVjpArgs {
+  int batch, n;
+  const T* H; int64_t sH;
+  const T* z;
+  const T* lb; int64_t slb;
+  const T* ub; int64_t sub;
+  const int32_t* status;
+  const T* gz;
+  T *gf, *glb, *gub, *gH;
+  int32_t* vstatus;
+};
 
 // Per-group LDS: the QSym exchange tile, the row vectors z, lb, ub, g and d,
 // and the packed tile (H on the way in, dL/dH on the way out).
@@ -109,52 +123,11 @@ __global__ __launch_bounds__(64) void box_vjp_quad_kernel(BoxVjpArgs<T> a) {
   if (code == MPCQP_STATUS_OPTIMAL && g_nonfinite) code = MPCQP_STATUS_NONFINITE;
   const bool run = live && code == MPCQP_STATUS_OPTIMAL;
 
-  // rows bi*BS + r of this lane: z, g and the row's state
-  // (0 free, 1 at lb, 2 at ub, 3 past n); lb == ub == z counts as "at lb"
-  T zr[BS], gr[BS];
+  // ------------------------------------- the step (box_vjp_core.hpp): d and nu
+  T zr[BS], dr[BS], nur[BS];
   int st[BS];
-#pragma unroll
-  for (int r = 0; r < BS; ++r) {
-    const int i = M.bi * BS + r;
-    zr[r] = zs[i];
-    gr[r] = gzs[i];
-    st[r] = i < n ? (zr[r] == lbs[i] ? 1 : (zr[r] == ubs[i] ? 2 : 0)) : 3;
-  }
-  // free-row mask of the group (rows bi*BS + r from the bj == 0 lanes)
-  unsigned fmask = 0;
-#pragma unroll
-  for (int r = 0; r < BS; ++r) {
-    const unsigned long long bal = __ballot(M.bj == 0 && st[r] == 0);
-#pragma unroll
-    for (int bb = 0; bb < 4; ++bb)
-      if ((bal >> (16 * g + 4 * bb)) & 1ull) fmask |= 1u << (bb * BS + r);
-  }
-  if (!run) fmask = 0;
-  // ---------------------------------------- M = SWEEP_F(H), wave-uniform trips
-  bool okp = true;
-  while (__any(fmask != 0)) {
-    const bool has = fmask != 0;
-    const int k = has ? __builtin_ctz(fmask) : 0;
-    fmask = has ? fmask & (fmask - 1) : 0u;
-    T colr[BS], colc[BS];
-    const T d = M.column(k, gb, colr, colc);
-    if (has) {
-      okp = okp && d > T(0);
-      sweep_col_ieee(M, k, d, colr, colc);
-    }
-  }
-  if (code == MPCQP_STATUS_OPTIMAL && !okp) code = MPCQP_STATUS_NOT_CONVEX;
-  const bool good = live && code == MPCQP_STATUS_OPTIMAL;
-  // ------------------------------------------------------ out = M [g_F; 0]
-  T w[BS], out[BS], dr[BS], nur[BS];
-#pragma unroll
-  for (int r = 0; r < BS; ++r) w[r] = (good && st[r] == 0) ? gr[r] : T(0);
-  M.matvec(w, gb, out);
-#pragma unroll
-  for (int r = 0; r < BS; ++r) {
-    dr[r] = (good && st[r] == 0) ? out[r] : T(0);
-    nur[r] = (good && (st[r] == 1 || st[r] == 2)) ? gr[r] - out[r] : T(0);
-  }
+  const bool good = box_vjp_step(M, gb, zs, gzs, lbs, ubs, n, g, run, zr, st, dr, nur);
+  if (run && !good) code = MPCQP_STATUS_NOT_CONVEX;
   if (live && M.bj == 0) {
 #pragma unroll
     for (int r = 0; r < BS; ++r) {
@@ -177,24 +150,7 @@ __global__ __launch_bounds__(64) void box_vjp_quad_kernel(BoxVjpArgs<T> a) {
       for (int r = 0; r < BS; ++r) ds[M.bi * BS + r] = dr[r];
     }
     lds_exchange();
-    if (M.bi >= M.bj) {
-      T dc[BS], zc[BS];
-#pragma unroll
-      for (int c = 0; c < BS; ++c) {
-        dc[c] = ds[M.bj * BS + c];
-        zc[c] = zs[M.bj * BS + c];
-      }
-#pragma unroll
-      for (int r = 0; r < BS; ++r)
-#pragma unroll
-        for (int c = 0; c < BS; ++c) {
-          const int i = M.bi * BS + r, j = M.bj * BS + c;
-          if (i < n && j <= i) {
-            const T v = i == j ? dr[r] * zr[r] : fma(dr[r], zc[c], dc[c] * zr[r]);
-            Ps[i * (i + 1) / 2 + j] = good ? v : T(0);
-          }
-        }
-    }
+    fold_dz(M, ds, zs, dr, zr, n, [&](int e, T v) { Ps[e] = good ? v : T(0); });
     lds_exchange();
     if (live) {
       T* Gb = a.gH + (int64_t)b * P;
@@ -216,14 +172,35 @@ static int launch_box_vjp(const BoxVjpArgs<T>& a, hipStream_t st) {
   return MPCQP_OK;
 }
 
-template <typename T>
-int solve_box_vjp_quad(const BoxVjpArgs<T>& a, hipStream_t st) {
-  return dispatch_bs<4>(a.n, [&](auto bs) {
-    return launch_box_vjp<T, decltype(bs)::value>(a, st);
-  });
-}
-
-template int solve_box_vjp_quad<double>(const BoxVjpArgs<double>&, hipStream_t);
-template int solve_box_vjp_quad<float>(const BoxVjpArgs<float>&, hipStream_t);
-
 }  // namespace mpcqp
+
+// The argument checks, all before any device work.
+extern "C" int mpcqp_solve_box_vjp(int dtype, int batch, int n, const void* H, int64_t strideH,
+                                   const void* z, const void* lb, int64_t strideLb, const void* ub,
+                                   int64_t strideUb, const int32_t* status, const void* gz,
+                                   void* gf, void* glb, void* gub, void* gH, int32_t* vstatus,
+                                   void* stream) {
+  using namespace mpcqp;
+  MPCQP_CHECK_ARG(dtype == MPCQP_F64 || dtype == MPCQP_F32, "mpcqp_solve_box_vjp: bad dtype %d",
+                  dtype);
+  MPCQP_CHECK_ARG(batch >= 0, "mpcqp_solve_box_vjp: batch < 0");
+  MPCQP_CHECK_ARG(n >= 1, "mpcqp_solve_box_vjp: n=%d < 1", n);
+  if (n > kBoxVjpMaxN) {
+    set_error("mpcqp_solve_box_vjp: n=%d above the limit %d", n, kBoxVjpMaxN);
+    return MPCQP_ENOTSUP;
+  }
+  if (batch == 0) return MPCQP_OK;
+  MPCQP_CHECK_ARG(H && z && gz, "mpcqp_solve_box_vjp: H, z, gz are required");
+  MPCQP_CHECK_ARG(strideH >= 0 && strideLb >= 0 && strideUb >= 0,
+                  "mpcqp_solve_box_vjp: negative stride");
+  auto run = [&](auto tp) {
+    using T = decltype(tp);
+    const BoxVjpArgs<T> a{batch, n, (const T*)H, strideH, (const T*)z, (const T*)lb, strideLb,
+                          (const T*)ub, strideUb, status, (const T*)gz, (T*)gf, (T*)glb, (T*)gub,
+                          (T*)gH, vstatus};
+    return dispatch_bs<4>(n, [&](auto bs) {
+      return launch_box_vjp<T, decltype(bs)::value>(a, (hipStream_t)stream);
+    });
+  };
+  return dtype == MPCQP_F64 ? run(0.0) : run(0.0f);
+}

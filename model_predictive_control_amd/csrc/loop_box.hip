@@ -35,6 +35,7 @@
 // instantiation) starts every step from the empty set.
 #include <type_traits>
 
+#include "box_vjp_core.hpp"
 #include "gi_box_core.hpp"
 #include "quad_api.hpp"
 
@@ -293,36 +294,19 @@ __global__ __launch_bounds__(64, (LoopOcc<T, BS>::w)) void box_loop_kernel(
 #endif
     bool nf = false;
     M.load_packed(Ps, n, nf);
-    // sweep H on the free rows of the warm-start set: free-row mask of the
-    // group (rows bi*BS + r from the bj == 0 lanes)
-    unsigned fmask = 0;
-#pragma unroll
-    for (int r = 0; r < BS; ++r) {
-      const unsigned long long bal = __ballot(M.bj == 0 && st[r] == 0);
-#pragma unroll
-      for (int bb = 0; bb < 4; ++bb)
-        if ((bal >> (16 * g + 4 * bb)) & 1ull) fmask |= 1u << (bb * BS + r);
-    }
+    // sweep H on the free rows of the warm-start set (box_vjp_core.hpp)
+    const unsigned fmask = free_row_mask(M, st, g);
     // NONFINITE goes before INFEASIBLE (code0 holds either), as in box_quad_kernel;
     // the step then skips gi_box_st, writes NaN and leaves the next one cold.
     // A failed step makes x NaN for the rest of the episode, whose steps
     // repeat the code of that first failure (its cause), not NONFINITE.
     int code = nfx ? MPCQP_STATUS_NONFINITE : code0;
     if (failed != MPCQP_STATUS_OPTIMAL) code = failed;
-    int sweeps = 0;
-    bool okp = true;
-    while (__any(fmask != 0)) {
-      const bool has = fmask != 0;
-      const int k = has ? __builtin_ctz(fmask) : 0;
-      fmask = has ? fmask & (fmask - 1) : 0u;
-      T colr[BS], colc[BS];
-      const T d = M.column(k, gb, colr, colc);
-      if (has) {
-        okp = okp && d > T(0);
-        M.sweep_col(k, T(1), d, colr, colc);
-        ++sweeps;
-      }
-    }
+    const int sweeps = __popc(fmask);
+    const bool okp = sweep_free_rows(M, gb, fmask, [&](int k, T d, const T(&colr)[BS],
+                                                       const T(&colc)[BS]) {
+      M.sweep_col(k, T(1), d, colr, colc);
+    });
     if (code == MPCQP_STATUS_OPTIMAL && !okp) code = MPCQP_STATUS_NOT_CONVEX;
     T zr[BS];
     int iters = 0;
@@ -421,18 +405,14 @@ static int launch_loop(const LoopArgsOf<T, AFFINE>& a, hipStream_t st) {
   return MPCQP_OK;
 }
 
-template <typename T, int NX, int NU, bool AFFINE>
-static int loop_bs(const LoopArgsOf<T, AFFINE>& a, hipStream_t st) {
-  return dispatch_bs<4>(a.n, [&](auto bs) {
-    return launch_loop<T, NX, NU, decltype(bs)::value, AFFINE>(a, st);
-  });
-}
-
 template <typename T, bool AFFINE>
 static int loop_t(const LoopArgsOf<T, AFFINE>& a, hipStream_t st) {
-  if (a.nx <= 2 && a.nu <= 1) return loop_bs<T, 2, 1, AFFINE>(a, st);
-  if (a.nx <= 2 && a.nu <= 2) return loop_bs<T, 2, 2, AFFINE>(a, st);
-  return loop_bs<T, 4, 2, AFFINE>(a, st);
+  return dispatch_nxnu(a.nx, a.nu, [&](auto cx, auto cu) {
+    return dispatch_bs<4>(a.n, [&](auto bs) {
+      return launch_loop<T, decltype(cx)::value, decltype(cu)::value, decltype(bs)::value,
+                         AFFINE>(a, st);
+    });
+  });
 }
 
 // Both entry points: g == w == nullptr and flags == 0 launch the kernels of
@@ -446,8 +426,7 @@ static int box_loop_entry(const char* who, int dtype, int batch, int nx, int nu,
                           int32_t* status, int max_iter, double tol, void* stream) {
   MPCQP_CHECK_ARG(dtype == MPCQP_F64 || dtype == MPCQP_F32, "%s: bad dtype %d", who, dtype);
   MPCQP_CHECK_ARG(batch >= 0 && N >= 1 && steps >= 0, "%s: bad sizes", who);
-  MPCQP_CHECK_ARG(nx >= 1 && nx <= 4 && nu >= 1 && nu <= 2 && N * nu <= 32,
-                  "%s: nx=%d nu=%d N=%d outside nx <= 4, nu <= 2, N*nu <= 32", who, nx, nu, N);
+  MPCQP_CHECK_LOOP_SIZES(who, nx, nu, N);
   MPCQP_CHECK_ARG((flags & ~MPCQP_LOOP_COLD) == 0, "%s: unknown flags 0x%x", who, flags);
   MPCQP_CHECK_ARG(H && F && A && Bm && x0 && xs && (steps == 0 || (us && status)),
                   "%s: H, F, A, B, x0, xs (and us, status for steps > 0) are required", who);

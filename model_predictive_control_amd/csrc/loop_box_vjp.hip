@@ -22,23 +22,21 @@
 // accumulators of gH (a packed tile), gF, glb, gub live in LDS and those of gA,
 // gB in one register of their owner lane.  Every accumulator entry is updated
 // by exactly one lane (no atomics) and written to HBM once, at the end.  Per
-// step the kernel rebuilds M = SWEEP_F(H) from the packed tile, exactly as the
-// stand-alone adjoint does (same load, same sweep order, same sweep body, same
-// product): a step's d and nu are those of mpcqp_solve_box_vjp on the same
-// data and no round-off drifts over T.  Per step and instance only z_t, x_t
+// step the kernel rebuilds M = SWEEP_F(H) from the packed tile and runs the
+// step function of box_vjp_core.hpp, the one the stand-alone adjoint runs: a
+// step's d and nu are those of mpcqp_solve_box_vjp on the same data and no
+// round-off drifts over T.  Per step and instance only z_t, x_t
 // and the given ones of gzs[t], gus[t], gxs[t] are read and gg[t], gw[t]
 // written; the rows of step t-1 are loaded (into the registers step t's rows
 // have just left) before step t's sweeps, so their latency lies under the
 // sweep loop -- the one-step-ahead pattern of the affine loop with t descending.
 //
-// The four groups of a wave hold different free sets: the sweep loop runs while
-// any group has a row left and every group passes every LDS publish.  An
-// instance whose outcome is not OPTIMAL gets exact zeros in every output, its
-// gg and gw rows included (rewritten in the epilogue by the lanes that wrote
-// them).  Division is IEEE (sweep_ieee.hpp; built without the
-// approximate-division flags).
+// An instance whose outcome is not OPTIMAL gets exact zeros in every output,
+// its gg and gw rows included (rewritten in the epilogue by the lanes that
+// wrote them).  Division is IEEE (built without the approximate-division
+// flags).
+#include "box_vjp_core.hpp"
 #include "quad_api.hpp"
-#include "sweep_ieee.hpp"
 
 namespace mpcqp {
 
@@ -239,54 +237,14 @@ __global__ __launch_bounds__(64) void box_loop_vjp_kernel(LoopVjpArgs<T> a) {
     if (t > 0) fetch(t - 1);
     const bool run = live && fcode == MPCQP_STATUS_OPTIMAL && !nonfin && !notconv;
 
+    // the step (box_vjp_core.hpp): d and nu from the packed tile (H was checked
+    // at stage-in: the load's flag is dropped)
     bool nfh = false;
     M.load_packed(Ps, n, nfh);
-    // rows bi*BS + r of this lane: z, gz and the row's state
-    // (0 free, 1 at lb, 2 at ub, 3 past n); lb == ub == z counts as "at lb"
-    T zr[BS], gr[BS];
+    T zr[BS], dr[BS], nur[BS];
     int st[BS];
-#pragma unroll
-    for (int r = 0; r < BS; ++r) {
-      const int i = M.bi * BS + r;
-      zr[r] = zs[i];
-      gr[r] = gzl[i];
-      st[r] = i < n ? (zr[r] == lbs[i] ? 1 : (zr[r] == ubs[i] ? 2 : 0)) : 3;
-    }
-    // free-row mask of the group (rows bi*BS + r from the bj == 0 lanes)
-    unsigned fmask = 0;
-#pragma unroll
-    for (int r = 0; r < BS; ++r) {
-      const unsigned long long bal = __ballot(M.bj == 0 && st[r] == 0);
-#pragma unroll
-      for (int bb = 0; bb < 4; ++bb)
-        if ((bal >> (16 * g + 4 * bb)) & 1ull) fmask |= 1u << (bb * BS + r);
-    }
-    if (!run) fmask = 0;
-    // -------------------------------------- M = SWEEP_F(H), wave-uniform trips
-    bool okp = true;
-    while (__any(fmask != 0)) {
-      const bool has = fmask != 0;
-      const int k = has ? __builtin_ctz(fmask) : 0;
-      fmask = has ? fmask & (fmask - 1) : 0u;
-      T colr[BS], colc[BS];
-      const T d = M.column(k, gb, colr, colc);
-      if (has) {
-        okp = okp && d > T(0);
-        sweep_col_ieee(M, k, d, colr, colc);
-      }
-    }
-    notconv = notconv || (run && !okp);
-    const bool good = run && okp;
-    // ---------------------------------------------------- out = M [gz_F; 0]
-    T w[BS], out[BS], dr[BS], nur[BS];
-#pragma unroll
-    for (int r = 0; r < BS; ++r) w[r] = (good && st[r] == 0) ? gr[r] : T(0);
-    M.matvec(w, gb, out);
-#pragma unroll
-    for (int r = 0; r < BS; ++r) {
-      dr[r] = (good && st[r] == 0) ? out[r] : T(0);
-      nur[r] = (good && (st[r] == 1 || st[r] == 2)) ? gr[r] - out[r] : T(0);
-    }
+    const bool good = box_vjp_step(M, gb, zs, gzl, lbs, ubs, n, g, run, zr, st, dr, nur);
+    notconv = notconv || (run && !good);
     // gg[t] = d, gw[t] = lam_{t+1}; d to LDS; glb, gub by the rows' owners
     if (M.bj == 0) {
 #pragma unroll
@@ -301,26 +259,8 @@ __global__ __launch_bounds__(64) void box_loop_vjp_kernel(LoopVjpArgs<T> a) {
     }
     if (good && a.gw && q < nx) a.gw[rb * nx + q] = ls[q];
     lds_exchange();
-    // gH += fold(d z'): the block owners on and below the diagonal
-    if (M.bi >= M.bj) {
-      T dc[BS], zc[BS];
-#pragma unroll
-      for (int c = 0; c < BS; ++c) {
-        dc[c] = ds[M.bj * BS + c];
-        zc[c] = zs[M.bj * BS + c];
-      }
-#pragma unroll
-      for (int r = 0; r < BS; ++r)
-#pragma unroll
-        for (int c = 0; c < BS; ++c) {
-          const int i = M.bi * BS + r, j = M.bj * BS + c;
-          if (i < n && j <= i) {
-            const T v = i == j ? dr[r] * zr[r] : fma(dr[r], zc[c], dc[c] * zr[r]);
-            const int e = i * (i + 1) / 2 + j;
-            GHs[e] = first ? v : GHs[e] + v;
-          }
-        }
-    }
+    // gH += fold(d z')
+    fold_dz(M, ds, zs, dr, zr, n, [&](int e, T v) { GHs[e] = first ? v : GHs[e] + v; });
     // gF += d x', gA += lam x', gB += lam u'
     for (int e = q; e < NMAX * NX; e += 16) {
       const int i = e / NX, j = e - i * NX;
@@ -402,19 +342,14 @@ static int launch_loop_vjp(const LoopVjpArgs<T>& a, hipStream_t st) {
   return MPCQP_OK;
 }
 
-template <typename T, int NX, int NU>
-static int loop_vjp_bs(const LoopVjpArgs<T>& a, hipStream_t st) {
-  return dispatch_bs<4>(a.n, [&](auto bs) {
-    return launch_loop_vjp<T, NX, NU, decltype(bs)::value>(a, st);
-  });
-}
-
-// the <NX, NU> instantiations of loop_box.hip
 template <typename T>
 static int loop_vjp_t(const LoopVjpArgs<T>& a, hipStream_t st) {
-  if (a.nx <= 2 && a.nu <= 1) return loop_vjp_bs<T, 2, 1>(a, st);
-  if (a.nx <= 2 && a.nu <= 2) return loop_vjp_bs<T, 2, 2>(a, st);
-  return loop_vjp_bs<T, 4, 2>(a, st);
+  return dispatch_nxnu(a.nx, a.nu, [&](auto cx, auto cu) {
+    return dispatch_bs<4>(a.n, [&](auto bs) {
+      return launch_loop_vjp<T, decltype(cx)::value, decltype(cu)::value, decltype(bs)::value>(
+          a, st);
+    });
+  });
 }
 
 }  // namespace mpcqp
@@ -432,8 +367,7 @@ extern "C" int mpcqp_mpc_box_loop_vjp(int dtype, int batch, int nx, int nu, int 
   const char* who = "mpcqp_mpc_box_loop_vjp";
   MPCQP_CHECK_ARG(dtype == MPCQP_F64 || dtype == MPCQP_F32, "%s: bad dtype %d", who, dtype);
   MPCQP_CHECK_ARG(batch >= 0 && N >= 1 && steps >= 0, "%s: bad sizes", who);
-  MPCQP_CHECK_ARG(nx >= 1 && nx <= 4 && nu >= 1 && nu <= 2 && N * nu <= 32,
-                  "%s: nx=%d nu=%d N=%d outside nx <= 4, nu <= 2, N*nu <= 32", who, nx, nu, N);
+  MPCQP_CHECK_LOOP_SIZES(who, nx, nu, N);
   if (batch == 0) return MPCQP_OK;
   MPCQP_CHECK_ARG(H && F && A && Bm, "%s: H, F, A, B are required", who);
   MPCQP_CHECK_ARG(steps == 0 || (xs && zs), "%s: xs and zs are required for steps > 0", who);

@@ -38,23 +38,20 @@ struct MpcArgsQ {
   T tol;
 };
 
-// box_vjp.hip: the adjoint of the box QP at its optimum z (n <= 32); every
-// output and status / vstatus may be NULL
-template <typename T>
-struct BoxVjpArgs {
-  int batch, n;
-  const T* H; int64_t sH;
-  const T* z;
-  const T* lb; int64_t slb;
-  const T* ub; int64_t sub;
-  const int32_t* status;
-  const T* gz;
-  T *gf, *glb, *gub, *gH;
-  int32_t* vstatus;
-};
-constexpr int kBoxVjpMaxN = 32;
-template <typename T>
-int solve_box_vjp_quad(const BoxVjpArgs<T>& a, hipStream_t st);
+// The one-launch box-MPC loop and its adjoint (loop_box.hip, loop_box_vjp.hip):
+// their size limits, and the <NX, NU> instantiation for a plant, as dispatch_bs
+// picks BS.  Calls f(integral_constant<int, NX>{}, integral_constant<int, NU>{}).
+#define MPCQP_CHECK_LOOP_SIZES(who, nx, nu, N)                                             \
+  MPCQP_CHECK_ARG(nx >= 1 && nx <= 4 && nu >= 1 && nu <= 2 && N * nu <= 32,                \
+                  "%s: nx=%d nu=%d N=%d outside nx <= 4, nu <= 2, N*nu <= 32", who, nx, nu, N)
+
+template <class F>
+inline auto dispatch_nxnu(int nx, int nu, F&& f) {
+  using std::integral_constant;
+  if (nx <= 2 && nu <= 1) return f(integral_constant<int, 2>{}, integral_constant<int, 1>{});
+  if (nx <= 2 && nu <= 2) return f(integral_constant<int, 2>{}, integral_constant<int, 2>{});
+  return f(integral_constant<int, 4>{}, integral_constant<int, 2>{});
+}
 
 template <typename T>
 int solve_box_quad(const BoxArgsQ<T>& a, hipStream_t st);
