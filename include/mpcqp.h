@@ -80,6 +80,13 @@ extern "C" {
 #define MPCQP_STATUS_NOT_CONVEX 2  /* non-positive pivot: H not positive definite */
 #define MPCQP_STATUS_INFEASIBLE 3  /* lb > ub, or polytope empty */
 #define MPCQP_STATUS_NONFINITE 4   /* NaN/Inf in the data */
+/* mpcqp_poly_solve / mpcqp_solve_poly test in this order: NOT_CONVEX (the
+   shared inverse met a non-positive pivot: every instance), NONFINITE (NaN/Inf
+   in x0 or f), INFEASIBLE from the bounds (hl > hu, hl = +inf, hu = -inf), then
+   the active set (INFEASIBLE when the ratio test finds the polytope empty).
+   A NaN in a row or box bound is answered INFEASIBLE, not NONFINITE: the bound
+   test is !(hl <= hu), which holds for a NaN.  Every status but OPTIMAL and
+   MAXITER writes NaN to z and y. */
 
 /* condense / MPC-step flags */
 #define MPCQP_TV 1  /* A, B are per-stage: N*nx*nx / N*nx*nu per instance */

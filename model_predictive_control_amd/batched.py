@@ -672,42 +672,87 @@ def mpc_box_loop_vjp(H, F, A, B, lb, ub, xs, zs, gxs=None, gus=None, gzs=None, *
 
 
 # ------------------------------------------------------------- polytope QP
+def _poly_box(v, n, dt, dev, name):
+    """lbz / ubz of the polytope QP: shared by the batch, a scalar or (n,)."""
+    t, _ = _bound(v, n, dt, dev)
+    if t is not None and tuple(t.shape) != (n,):
+        raise ValueError(f"{name} must be a scalar or ({n},), got {tuple(t.shape)}")
+    return t
+
+
+def _poly_vec(t, width, name):
+    """(stride, batch) of a (width,) shared or (batch, width) per-instance operand."""
+    if t is None:
+        return 0, None
+    if t.ndim not in (1, 2) or t.shape[-1] != width:
+        raise ValueError(f"{name} must be ({width},) or (batch, {width}), got {tuple(t.shape)}")
+    return (width, int(t.shape[0])) if t.ndim == 2 else (0, None)
+
+
+def _poly_rows(hl, hu, m):
+    """(stride, batch) of the row bounds: both shared or both per instance."""
+    (sl, bl), (su, bu) = _poly_vec(hl, m, "hl"), _poly_vec(hu, m, "hu")
+    if hl is not None and hu is not None and hl.ndim != hu.ndim:
+        raise ValueError("hl and hu must both be shared or both per instance, got "
+                         f"{tuple(hl.shape)} and {tuple(hu.shape)}")
+    if bl is not None and bu is not None and bl != bu:
+        raise ValueError(f"hl and hu have different batch sizes {bl} and {bu}")
+    return max(sl, su), bl if bl is not None else bu
+
+
+def _poly_out(out, batch, n, mt, dt, dev):
+    """z, y, status of a polytope solve: allocated, or the checked ``out``
+    triple (contiguous, of dtype ``dt`` on the operands' device ``dev``)."""
+    shapes = (("z", (batch, n), dt), ("y", (batch, mt), dt), ("status", (batch,), torch.int32))
+    if out is None:
+        return tuple(torch.empty(shp, dtype=kd, device=dev) for _, shp, kd in shapes)
+    if not isinstance(out, (tuple, list)) or len(out) != 3:
+        raise ValueError("out must be a triple (z, y, status)")
+    for t, (name, shp, kd) in zip(out, shapes):
+        if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shp or t.dtype != kd
+                or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"out {name} must be a contiguous {kd} tensor of shape {shp} on {dev}")
+    return tuple(out)
+
+
 def solve_poly(H, f, G=None, hl=None, hu=None, lbz=None, ubz=None, *, max_iter: int = 0,
-               tol: float = 0.0):
+               tol: float = 0.0, out: tuple | None = None):
     """Batched  min 1/2 z'Hz + f'z  s.t.  hl <= G z <= hu,  lbz <= z <= ubz.
 
-    H (packed, shared) and G (m, n) shared; f, hl, hu per instance or shared.
-    Returns (z, y, status); y are the multipliers of the rows [G; I].
+    H (packed, shared) and G (m, n) shared; f (n,) | (b, n); hl, hu (m,) |
+    (b, m), both shared or both per instance; lbz, ubz a scalar or (n,).
+    Returns (z, y, status); y are the multipliers of the rows [G; I]
+    (``out``: a preallocated contiguous triple to write them to).  Malformed
+    operands raise ValueError before anything is launched.
     """
     dt, dev = f.dtype, f.device
     f = _dev(f, dt, dev)
     H = _dev(H, dt, dev)
+    if f.ndim not in (1, 2):
+        raise ValueError(f"f must be (n,) or (batch, n), got {tuple(f.shape)}")
     n = int(f.shape[-1])
     if H.ndim != 1:
         raise ValueError("solve_poly: H must be shared (packed, 1-D)")
-    m = 0 if G is None else int(G.shape[0])
+    if H.shape[0] != n * (n + 1) // 2:
+        raise ValueError(f"H must be packed lower with {n * (n + 1) // 2} entries for f of width "
+                         f"{n}, got {tuple(H.shape)}")
     G = _dev(G, dt, dev)
-    sf, bf = _inst(f, 1, "f")
+    if G is not None and (G.ndim != 2 or G.shape[1] != n):
+        raise ValueError(f"G must be (m, {n}), got {tuple(G.shape)}")
+    m = 0 if G is None else int(G.shape[0])
+    sf, bf = _poly_vec(f, n, "f")
     hl = _dev(hl, dt, dev)
     hu = _dev(hu, dt, dev)
-    sh, bh = 0, None
-    for h in (hl, hu):
-        if h is not None:
-            s, b = _inst(h, 1, "h")
-            sh, bh = max(sh, s), b if b is not None else bh
-    if hl is not None and hu is not None and hl.shape != hu.shape:
-        raise ValueError("hl and hu must have the same shape")
-    lbz_t, _ = _bound(lbz, n, dt, dev)
-    ubz_t, _ = _bound(ubz, n, dt, dev)
+    sh, bh = _poly_rows(hl, hu, m)
+    lbz_t = _poly_box(lbz, n, dt, dev, "lbz")
+    ubz_t = _poly_box(ubz, n, dt, dev, "ubz")
     nbox = 1 if (lbz_t is not None or ubz_t is not None) else 0
     mt = m + (n if nbox else 0)
     batch = _batch_of((sf, bf), (sh, bh))
+    z, y, status = _poly_out(out, batch, n, mt, dt, dev)
     lib = _lib()
     wsb = int(lib.mpcqp_solve_poly_workspace(_code(dt), batch, n, m, nbox))
     ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
-    z = torch.empty((batch, n), dtype=dt, device=dev)
-    y = torch.empty((batch, mt), dtype=dt, device=dev)
-    status = torch.empty((batch,), dtype=torch.int32, device=dev)
     rc = lib.mpcqp_solve_poly(_code(dt), batch, n, m, _ptr(H), _ptr(f), sf, _ptr(G), _ptr(hl),
                               _ptr(hu), sh, _ptr(lbz_t), _ptr(ubz_t), _ptr(z), _ptr(y),
                               _ptr(status), int(max_iter), float(tol), _ptr(ws), wsb, _stream())
@@ -732,12 +777,18 @@ class PolyQP:
         self.dtype, self.device = dt, dev
         self.H = _dev(H, dt, dev)
         self.n = n = isqrt_packed(int(self.H.shape[-1]))
+        if self.H.ndim != 1:
+            raise ValueError("PolyQP: H must be shared (packed, 1-D)")
         self.G = _dev(G, dt, dev)
+        if G is not None and (self.G.ndim != 2 or self.G.shape[1] != n):
+            raise ValueError(f"G must be (m, {n}), got {tuple(self.G.shape)}")
         self.m = 0 if G is None else int(self.G.shape[0])
         self.F = _dev(F, dt, dev)
+        if F is not None and (self.F.ndim != 2 or self.F.shape[0] != n):
+            raise ValueError(f"F must be ({n}, nx), got {tuple(self.F.shape)}")
         self.nx = 0 if F is None else int(self.F.shape[-1])
-        self.lbz, _ = _bound(lbz, n, dt, dev)
-        self.ubz, _ = _bound(ubz, n, dt, dev)
+        self.lbz = _poly_box(lbz, n, dt, dev, "lbz")
+        self.ubz = _poly_box(ubz, n, dt, dev, "ubz")
         self.nbox = 1 if (self.lbz is not None or self.ubz is not None) else 0
         self.mt = self.m + (n if self.nbox else 0)
         lib = _lib()
@@ -749,23 +800,20 @@ class PolyQP:
 
     def solve(self, x0=None, f=None, hl=None, hu=None, *, max_iter: int = 0, tol: float = 0.0,
               out: tuple | None = None):
-        """Returns (z (b, n), y (b, m_total), status (b,))."""
+        """x0 (nx,) | (b, nx), f (n,) | (b, n), hl and hu (m,) | (b, m), both
+        shared or both per instance; ``out`` a preallocated (z, y, status).
+        Returns (z (b, n), y (b, m_total), status (b,))."""
         dt, dev, n = self.dtype, self.device, self.n
         x0, f = _dev(x0, dt, dev), _dev(f, dt, dev)
         hl, hu = _dev(hl, dt, dev), _dev(hu, dt, dev)
-        sX, bX = _inst(x0, 1, "x0")
-        sf, bf = _inst(f, 1, "f")
-        sh, bh = 0, None
-        for h in (hl, hu):
-            if h is not None:
-                sh, bh = _inst(h, 1, "h")
+        if x0 is not None and self.nx == 0:
+            raise ValueError("x0 given, but this PolyQP has no x0 -> gradient map F")
+        sX, bX = _poly_vec(x0, self.nx, "x0")
+        sf, bf = _poly_vec(f, n, "f")
+        sh, bh = _poly_rows(hl, hu, self.m)
         batch = _batch_of((sX, bX), (sf, bf), (sh, bh))
-        if out is None:
-            z = torch.empty((batch, n), dtype=dt, device=dev)
-            y = torch.empty((batch, self.mt), dtype=dt, device=dev)
-            status = torch.empty((batch,), dtype=torch.int32, device=dev)
-        else:
-            z, y, status = out
+        # self.device may lack an index ("cuda"); the workspace's has one, as out's do
+        z, y, status = _poly_out(out, batch, n, self.mt, dt, self.ws.device)
         rc = _lib().mpcqp_poly_solve(_code(dt), batch, n, self.m, self.nbox, self.nx,
                                      _ptr(self.ws), _ptr(x0), sX, _ptr(f), sf, _ptr(hl), _ptr(hu),
                                      sh, _ptr(self.lbz), _ptr(self.ubz), _ptr(z), _ptr(y),
