@@ -43,97 +43,61 @@ STATUS_INFEASIBLE = 3
 STATUS_NONFINITE = 4
 STATUS_NAMES = {0: "optimal", 1: "max_iter", 2: "not_convex", 3: "infeasible", 4: "nonfinite"}
 
-# every symbol include/mpcqp.h declares, with (restype, argtypes)
-_vp = ctypes.c_void_p
-_i = ctypes.c_int
-_i64 = ctypes.c_int64
-_d = ctypes.c_double
-SIGNATURES = {
-    "mpcqp_abi_version": (_i, []),
-    "mpcqp_last_error": (ctypes.c_char_p, []),
-    "mpcqp_max_box_n": (_i, [_i]),
-    "mpcqp_condense": (_i, [_i, _i, _i, _i, _i, _i,
-                            _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
-                            _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mpcqp_solve_box": (_i, [_i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
-                             _vp, _vp, _i, _d, _vp]),
-    "mpcqp_solve_box_vjp": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp,
-                                 _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mpcqp_mpc_box": (_i, [_i, _i, _i, _i, _i, _i,
-                           _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
-                           _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i, _d, _vp]),
-    "mpcqp_solve_poly_workspace": (_i64, [_i, _i, _i, _i, _i]),
-    "mpcqp_solve_poly": (_i, [_i, _i, _i, _i, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp,
-                              _vp, _vp, _vp, _i, _d, _vp, _i64, _vp]),
-    "mpcqp_poly_workspace": (_i64, [_i, _i, _i, _i, _i]),
-    "mpcqp_poly_setup": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
-    "mpcqp_poly_solve": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64,
-                              _vp, _vp, _vp, _vp, _vp, _i, _d, _vp]),
-    "mpcqp_max_qp_size": (_i, [_i]),
-    "mpcqp_solve_qp": (_i, [_i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64,
-                            _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i, _d, _vp]),
-    "mpcqp_solve_qp_workspace": (ctypes.c_size_t, [_i, _i, _i, _i]),
-    "mpcqp_sweep": (_i, [_i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i, _vp, _vp]),
-    "mpcqp_solve_qp_ws": (_i, [_i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64,
-                               _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i, _d, _vp, ctypes.c_size_t,
-                               _vp]),
-    "mpcqp_solve_box_ws": (_i, [_i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
-                                _vp, _vp, _i, _d, _vp, ctypes.c_size_t, _vp]),
-    "mpcqp_mpc_qp_workspace": (ctypes.c_size_t, [_i, _i, _i, _i, _i, _i]),
-    "mpcqp_mpc_qp": (_i, [_i, _i, _i, _i, _i, _i,
-                          _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
-                          _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64,
-                          _vp, _vp, _vp, _vp, _i, _d, _vp, ctypes.c_size_t, _vp]),
-    "mpcqp_mpc_ipm_workspace": (ctypes.c_size_t, [_i, _i, _i, _i, _i]),
-    "mpcqp_mpc_ipm": (_i, [_i, _i, _i, _i, _i, _i,
-                           _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
-                           _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
-                           _vp, _i64, _vp, _i64,
-                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _i, _d, _vp,
-                           ctypes.c_size_t, _vp]),
-    "mpcqp_mpc_box_loop": (_i, [_i] * 6 + [_vp, _i64] * 7 + [_vp] * 3 + [_vp, _i, _d, _vp]),
-    "mpcqp_mpc_box_loop_affine": (_i, [_i] * 7 + [_vp, _i64] * 7 + [_vp, _i64, _vp] + [_vp] * 3 +
-                                  [_vp, _i, _d, _vp]),
-    "mpcqp_mpc_box_loop_vjp": (_i, [_i] * 6 + [_vp, _i64] * 6 + [_vp] * 17),
-    "mpcqp_mpc_poly_loop": (_i, [_i] * 9 + [_vp] * 5 + [_i64, _vp, _vp, _i64] + [_vp] * 8 +
-                            [_i, _d, _vp]),
-    "mpcqp_mpc_poly_loop_soft": (_i, [_i] * 9 + [_vp] * 5 + [_i64, _vp, _vp, _i64] + [_vp] * 11 +
-                                 [_i, _d, _vp]),
-    "mpcqp_mpc_poly_loop_affine_workspace": (ctypes.c_size_t, [_i] * 7),
-    "mpcqp_mpc_poly_loop_affine": (_i, [_i] * 9 + [_vp] * 5 + [_i64, _vp, _vp, _i64] + [_vp] * 5 +
-                                   [_vp, _i64, _vp, _i64, _vp, ctypes.c_size_t] + [_vp] * 6 +
-                                   [_i, _d, _vp]),
-    "mpcqp_mpc_qp_profile": (_i, [_i]),
-    "mpcqp_mpc_qp_stage_ms": (_i, [ctypes.POINTER(ctypes.c_float)]),
-    "mpcqp_bicycle_hessian": (_i, [_i, _i, _i, _d, ctypes.POINTER(ctypes.c_double), _i, _vp, _vp,
-                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mpcqp_bicycle_hessian_convex": (_i, [_i, _i, _i, _d, ctypes.POINTER(ctypes.c_double), _i, _vp,
-                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp]),
-    "mpcqp_bicycle_linearise": (_i, [_i, _i, _i, _d, ctypes.POINTER(ctypes.c_double), _i, _vp,
-                                     _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "mpcqp_bicycle_sqp_step": (_i, [_i, _i, _i, _d, ctypes.POINTER(ctypes.c_double), _i, _vp, _i64,
-                                    _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp,
-                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp]),
-    "mpcqp_bicycle_sqp_solve_workspace": (ctypes.c_size_t, [_i, _i]),
-    "mpcqp_bicycle_sqp_solve": (_i, [_i, _i, _i, _d, ctypes.POINTER(ctypes.c_double), _i, _i, _vp,
-                                     _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp,
-                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _d, _vp,
-                                     ctypes.c_size_t, _vp]),
-    "mpcqp_bicycle_mpc_loop": (_i, [_i, _i, _i, _i, _d, ctypes.POINTER(ctypes.c_double), _i, _i,
-                                    ctypes.POINTER(ctypes.c_double), _i, _i, _vp, _vp, _vp, _vp,
-                                    _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                    _vp, _vp, _i, _i, _i, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp,
-                                    _vp, ctypes.c_size_t, _vp]),
-    "mpcqp_bicycle_plant": (_i, [_i, _i, _d, ctypes.POINTER(ctypes.c_double), _i, _i, _vp, _vp,
-                                 _i64, _vp, _vp, _vp]),
-    "mpcqp_sqp_shift": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp]),
-    "mpcqp_riccati": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
-                           _vp, _i64, _vp, _vp, _vp]),
-    "mpcqp_bicycle_rti": (_i, [_i, _i, _i, _d, ctypes.POINTER(ctypes.c_double), _vp, _i64, _vp, _i64,
-                               _vp, _vp, _vp, _vp, _vp]),
-    "mpcqp_gemv": (_i, [_i, _i, _i, _i, _d, _vp, _i64, _vp, _i64, _d, _vp, _i64, _vp]),
-    "mpcqp_rollout": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+# Every symbol include/mpcqp.h declares: the return kind, then one letter per
+# argument in the prototype's order (blanks only group them: "pl" is a pointer
+# with its instance stride).  tests/test_abi.py checks each entry against the
+# header's prototype.
+_KINDS = {"i": ctypes.c_int, "l": ctypes.c_int64, "z": ctypes.c_size_t, "d": ctypes.c_double,
+          "p": ctypes.c_void_p, "s": ctypes.c_char_p, "D": ctypes.POINTER(ctypes.c_double),
+          "F": ctypes.POINTER(ctypes.c_float)}
+_TABLE = {
+    "mpcqp_abi_version": "i",
+    "mpcqp_last_error": "s",
+    "mpcqp_max_box_n": "i i",
+    "mpcqp_condense": "i iiiiii pl pl pl pl pl pl pl ppppppp",
+    "mpcqp_solve_box": "i iii pl pl pl pl ppid p",
+    "mpcqp_solve_box_vjp": "i iii pl ppl pl pppppppp",
+    "mpcqp_mpc_box": "i iiiiii pl pl pl pl pl pl pl pl pl ppid p",
+    "mpcqp_solve_poly_workspace": "l iiiii",
+    "mpcqp_solve_poly": "i iiii ppl pppl pppppid pl p",
+    "mpcqp_poly_workspace": "l iiiii",
+    "mpcqp_poly_setup": "i iiiii ppppl p",
+    "mpcqp_poly_solve": "i iiiiii ppl pl ppl pppppid p",
+    "mpcqp_max_qp_size": "i i",
+    "mpcqp_solve_qp": "i iiii pl pl pl ppl pl pl pppid p",
+    "mpcqp_solve_qp_workspace": "z iiii",
+    "mpcqp_sweep": "i iiii pl pl pi pp",
+    "mpcqp_solve_qp_ws": "i iiii pl pl pl ppl pl pl pppid pz p",
+    "mpcqp_solve_box_ws": "i iii pl pl pl pl ppid pz p",
+    "mpcqp_mpc_qp_workspace": "z iiiiii",
+    "mpcqp_mpc_qp": "i iiiiii pl pl pl pl pl pl pl ppl pl pl ppppid pz p",
+    "mpcqp_mpc_ipm_workspace": "z iiiii",
+    "mpcqp_mpc_ipm": "i iiiiii pl pl pl pl pl pl pl ppl pl pl pl pl pl pppppppiid pz p",
+    "mpcqp_mpc_box_loop": "i iiiiii pl pl pl pl pl pl pl ppppid p",
+    "mpcqp_mpc_box_loop_affine": "i iiiiiii pl pl pl pl pl pl pl pl pppppid p",
+    "mpcqp_mpc_box_loop_vjp": "i iiiiii pl pl pl pl pl pl ppppppppppppppppp",
+    "mpcqp_mpc_poly_loop": "i iiiiiiiii pppppl ppl ppppppppid p",
+    "mpcqp_mpc_poly_loop_soft": "i iiiiiiiii pppppl ppl pppppppppppid p",
+    "mpcqp_mpc_poly_loop_affine_workspace": "z iiiiiii",
+    "mpcqp_mpc_poly_loop_affine": "i iiiiiiiii pppppl ppl ppppppl pl pz ppppppid p",
+    "mpcqp_mpc_qp_profile": "i i",
+    "mpcqp_mpc_qp_stage_ms": "i F",
+    "mpcqp_bicycle_hessian": "i iiidDi ppppppppp",
+    "mpcqp_bicycle_hessian_convex": "i iiidDi ppppppppd ppp",
+    "mpcqp_bicycle_linearise": "i iiidDi pl pl ppppp",
+    "mpcqp_bicycle_sqp_step": "i iiidDi pl pppppl ppl pppppppppppppd p",
+    "mpcqp_bicycle_sqp_solve_workspace": "z ii",
+    "mpcqp_bicycle_sqp_solve": "i iiidDii pl pppppl ppl pppppppppppiid pz p",
+    "mpcqp_bicycle_mpc_loop": "i iiiidDiiDii pppppl ppl pppppppppiiidd pppppppz p",
+    "mpcqp_bicycle_plant": "i iidDii ppl ppp",
+    "mpcqp_sqp_shift": "i iii pppppppd p",
+    "mpcqp_riccati": "i iiiii pl pl pl pl pl ppp",
+    "mpcqp_bicycle_rti": "i iiidD pl pl ppppp",
+    "mpcqp_gemv": "i iiiid pl pld pl p",
+    "mpcqp_rollout": "i iiiii pppppp",
 }
+SIGNATURES = {name: (_KINDS[s[0]], [_KINDS[c] for c in s[1:].replace(" ", "")])
+              for name, s in _TABLE.items()}
 
 ABI_VERSION = 1
 

@@ -16,7 +16,6 @@ Shape conventions (batch-outermost, row-major):
 from __future__ import annotations
 
 import ctypes
-
 import math
 
 import torch
@@ -24,12 +23,21 @@ import torch
 from . import _native as nat
 
 __all__ = [
-    "condense", "solve_box", "solve_box_vjp", "mpc_box", "mpc_box_loop", "mpc_box_loop_vjp", "mpc_poly_loop", "tracking_terms", "mpc_qp", "mpc_ipm", "solve_poly", "solve_qp", "sweep", "riccati", "gemv",
-    "rollout", "bicycle_rti", "bicycle_linearise", "bicycle_hessian", "bicycle_sqp_step",
-    "pack_lower", "unpack_lower", "status_code", "status_iters", "workspace_bytes",
+    "condense", "solve_box", "solve_box_vjp", "mpc_box", "mpc_box_loop", "mpc_box_loop_vjp",
+    "mpc_poly_loop", "tracking_terms", "mpc_qp", "mpc_ipm", "solve_poly", "solve_qp", "sweep",
+    "riccati", "gemv", "rollout", "bicycle_rti", "bicycle_linearise", "bicycle_hessian",
+    "bicycle_sqp_step", "pack_lower", "unpack_lower", "status_code", "status_iters",
+    "workspace_bytes",
 ]
 
 
+# ------------------------------------------------------------- marshalling
+# Everything between a wrapper's Python operands and its C call.  The wrappers
+# reach _lib, _stream, _dev and _workspace through the module's globals, so a
+# replacement assigned to one of these names takes effect (tools/ab_libs.py,
+# tests/_batched_record.py).  Nothing here reads device memory or synchronises:
+# shapes, dtypes, strides and data_ptr() only, so the wrappers can be captured
+# into a HIP graph.
 def _lib():
     return nat.load()
 
@@ -103,7 +111,10 @@ def _inst(t, base_ndim: int, name: str):
     if t.ndim == base_ndim:
         return 0, None
     if t.ndim == base_ndim + 1:
-        return int(t[0].numel()), int(t.shape[0])
+        b = int(t.shape[0])
+        if b == 0:      # what indexing the first instance of an empty batch raises
+            raise IndexError("index 0 is out of bounds for dimension 0 with size 0")
+        return t.numel() // b, b
     raise ValueError(f"{name}: expected {base_ndim} or {base_ndim + 1} dims, got {tuple(t.shape)}")
 
 
@@ -112,6 +123,153 @@ def _batch_of(*pairs):
     if len(bs) > 1:
         raise ValueError(f"inconsistent batch sizes {sorted(bs)}")
     return bs.pop() if bs else 1
+
+
+def _inst_one(t, base_ndim: int, name: str, when: bool = True):
+    """``_inst`` where a leading dimension of 1 counts as shared if ``when``
+    (a shared plant condenses to one instance)."""
+    s, b = _inst(t, base_ndim, name)
+    return (0, None) if b == 1 and when else (s, b)
+
+
+def _dt_dev(A):
+    """(dtype, device) of a call, from its leading operand."""
+    dt = A.dtype if isinstance(A, torch.Tensor) else torch.float64
+    dev = A.device if isinstance(A, torch.Tensor) else torch.device("cuda")
+    return dt, dev
+
+
+def _weight_r(R, nu: int):
+    """R as (nu, nu) (or batched).  FHC.py:141 passes R with shape (1,), which
+    NumPy broadcasts; a 1-D R is accepted only for nu == 1 (shape (1,)) -- a
+    vector of diagonal weights must be given as a matrix (torch.diag)."""
+    if R.ndim == 1:
+        if R.shape[0] != 1 or nu != 1:
+            raise ValueError(f"R of shape {tuple(R.shape)} with nu={nu}: pass an (nu, nu) matrix")
+        return R.reshape(1, 1).contiguous()
+    return R
+
+
+def _plant(A, B, Q, R, Qf, x0, c, tv: bool):
+    """The plant operands of condense / mpc_box / mpc_qp / mpc_ipm, converted:
+    returns (dt, dev, nx, nu, keep, insts, head).  ``keep`` holds the tensors
+    (A, B, Q, R, Qf, c, x0) -- ``_dev`` may have made copies that nothing else
+    references -- so a wrapper holds on to it until its C call has returned.
+    ``insts`` are their (stride, batch) pairs and ``head`` the 14 values
+    ``ptr(A), sA, .. ptr(c), sC, ptr(x0), sX`` of the C prototypes."""
+    dt, dev = _dt_dev(A)
+    A, B, Q, R, Qf, x0, c = [_dev(v, dt, dev) for v in (A, B, Q, R, Qf, x0, c)]
+    nx, nu = int(B.shape[-2]), int(B.shape[-1])
+    R = _weight_r(R, nu)
+    base = 3 if tv else 2
+    keep = (A, B, Q, R, Qf, c, x0)
+    insts = (_inst(A, base, "A"), _inst(B, base, "B"), _inst(Q, 2, "Q"), _inst(R, 2, "R"),
+             _inst(Qf, 2, "Qf"), _inst(c, 2, "c"), _inst(x0, 1, "x0"))
+    head = []
+    for t, (s, _) in zip(keep, insts):
+        head += (None if t is None else t.data_ptr(), s)
+    return dt, dev, nx, nu, keep, insts, head
+
+
+def _bound(v, n, dt, dev):
+    """(tensor, stride, batch) of a box bound: None, a scalar (Python number or
+    0-d tensor, filled to (n,)), shared or per instance."""
+    if v is None:
+        return None, 0, None
+    if not isinstance(v, torch.Tensor) and (isinstance(v, (int, float))):
+        return torch.full((n,), float(v), dtype=dt, device=dev), 0, None
+    t = _dev(v, dt, dev)
+    if t.ndim == 0:
+        return t.expand(n).contiguous(), 0, None
+    return (t, *_inst(t, 1, "bound"))
+
+
+def _alloc(spec: dict, dev, out=None, *, keyed: bool = False, check: bool = False):
+    """The output tensors of a call.  ``spec`` maps each output's name, in the
+    order of the result, to (shape, dtype), or to None for one that is not
+    produced.  ``keyed``: ``out`` is a dict (or None) and the result a copy of
+    it with the missing outputs allocated; otherwise ``out`` is a sequence in
+    the order of ``spec``, returned as it is, and None allocates them all.
+    ``check``: what the caller supplied must be contiguous with the shape and
+    dtype of ``spec`` (sequence form: also tensors on ``dev``, and as many as
+    ``spec`` has); without it the caller's objects are passed on unexamined."""
+    if keyed or out is None:
+        o = dict(out or {}) if keyed else {}
+        for k, v in spec.items():
+            if k not in o:
+                o[k] = None if v is None else torch.empty(v[0], dtype=v[1], device=dev)
+            elif check and (o[k].shape != v[0] or o[k].dtype != v[1] or not o[k].is_contiguous()):
+                raise ValueError(f"out[{k!r}] must be a contiguous {v[1]} tensor of shape {v[0]}")
+        return o if keyed else tuple(o.values())
+    if not check:
+        return out
+    if not isinstance(out, (tuple, list)) or len(out) != len(spec):
+        raise ValueError(f"out must be a triple ({', '.join(spec)})")
+    for t, (name, (shp, kd)) in zip(out, spec.items()):
+        if (not isinstance(t, torch.Tensor) or t.shape != shp or t.dtype != kd or t.device != dev
+                or not t.is_contiguous()):
+            raise ValueError(f"out {name} must be a contiguous {kd} tensor of shape {shp} on {dev}")
+    return tuple(out)
+
+
+def _row_pair(lo, hi, policy: str, side, mixed: str = ""):
+    """A lower/upper pair of bounds that the C call reads with ONE instance
+    stride.  ``side(t, k)`` validates one side (k = 0 lower, 1 upper; t may be
+    None) with its caller's message and returns (tensor, stride, batch).  Where
+    one side is shared and the other per instance, ``policy`` decides:
+
+    * "broadcast": both are expanded to the per-instance shape, so the shared
+      stride is never applied to a per-instance buffer or the reverse (which
+      would read past the shared side's end);
+    * "raise": ValueError(``mixed``), ``{lo}`` and ``{hi}`` being the shapes;
+    * "equal": the shapes must be equal to begin with, else ValueError(``mixed``)
+      before either side is looked at.
+
+    Returns (lo, hi, stride, batch of lo, batch of hi)."""
+    both = lo is not None and hi is not None
+    if policy == "equal" and both and lo.shape != hi.shape:
+        raise ValueError(mixed)
+    lo, sl, bl = side(lo, 0)
+    hi, su, bu = side(hi, 1)
+    if policy == "raise" and both and (bl is None) != (bu is None):
+        raise ValueError(mixed.format(lo=tuple(lo.shape), hi=tuple(hi.shape)))
+    if policy == "broadcast" and (bl is not None or bu is not None):
+        shape = (lo if bl is not None else hi).shape
+        lo, hi = (None if v is None else v.expand(shape).contiguous() for v in (lo, hi))
+    return lo, hi, max(sl, su), bl, bu
+
+
+def _bound_pair(lo, hi, b: int, width: int, what: str):
+    """The bound pairs of the bicycle entry points: each side None, (width,)
+    shared or (b, width); a shared side next to a per-instance one is
+    broadcast to (b, width) (``_row_pair``).  Returns (lo, hi, stride)."""
+    def side(v, _):
+        if v is None:
+            return None, 0, None
+        if tuple(v.shape) not in ((width,), (b, width)):
+            raise ValueError(f"{what}: shape {tuple(v.shape)} is neither ({width},) nor ({b}, {width})")
+        return (v, width, b) if v.ndim == 2 else (v, 0, None)
+
+    return _row_pair(lo, hi, "broadcast", side)[:3]
+
+
+def _bike_params(params):
+    return (ctypes.c_double * 4)(params.axis_front, params.axis_rear, params.acceleration,
+                                 params.friction)
+
+
+def _sqp_state(state: dict):
+    """The pointer run (rho, kkt, mu, flags, fix) of the bicycle SQP state."""
+    return (_ptr(state["rho"]), _ptr(state["kkt"]), _ptr(state["mu"]), _ptr(state["flags"]),
+            _ptr(state.get("fix")))
+
+
+def _check_tensors(who: str, dev, specs):
+    """Each (name, tensor, shape, dtype) of ``specs`` is contiguous, of that
+    shape and dtype, on ``dev``."""
+    for name, t, shp, dt in specs:
+        if tuple(t.shape) != shp or t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{who}: {name} must be a contiguous {dt} device tensor of shape {shp}")
 
 
 def status_code(status: torch.Tensor) -> torch.Tensor:
@@ -156,34 +314,18 @@ def condense(A, B, Q, R, Qf, N: int, x0=None, c=None, *, tv: bool = False,
     as its lower block triangle, (b, nx*nu*N*(N+1)/2) (``MPCQP_GAM_PACKED``;
     ``unpack_gam`` restores the dense (b, N*nx, N*nu) form).
     """
-    dt = A.dtype if isinstance(A, torch.Tensor) else torch.float64
-    dev = A.device if isinstance(A, torch.Tensor) else torch.device("cuda")
-    A, B, Q, R, Qf = (_dev(v, dt, dev) for v in (A, B, Q, R, Qf))
-    x0, c = _dev(x0, dt, dev), _dev(c, dt, dev)
-    nx, nu = int(B.shape[-2]), int(B.shape[-1])
-    R = _weight_r(R, nu)
-    base = 3 if tv else 2
-    sA, bA = _inst(A, base, "A")
-    sB, bB = _inst(B, base, "B")
-    sQ, bQ = _inst(Q, 2, "Q")
-    sR, bR = _inst(R, 2, "R")
-    sQf, bQf = _inst(Qf, 2, "Qf")
-    sC, bC = _inst(c, 2, "c")
-    sX, bX = _inst(x0, 1, "x0")
-    batch = _batch_of((sA, bA), (sB, bB), (sQ, bQ), (sR, bR), (sQf, bQf), (sC, bC), (sX, bX))
+    dt, dev, nx, nu, keep, insts, head = _plant(A, B, Q, R, Qf, x0, c, tv)
+    batch = _batch_of(*insts)
     n = N * nu
     want = set(outputs) | {"H"}
-    out = dict(out or {})
+    out = out or {}
     shapes = {"H": (batch, n * (n + 1) // 2), "F": (batch, n, nx), "f": (batch, n),
-              "Gam": (batch, nx * nu * N * (N + 1) // 2) if gam_packed else (batch, N * nx, n), "Phi": (batch, N * nx, nx), "xbar": (batch, N * nx)}
-    for k in want:
-        if k not in out:
-            out[k] = torch.empty(shapes[k], dtype=dt, device=dev)
+              "Gam": (batch, nx * nu * N * (N + 1) // 2) if gam_packed else (batch, N * nx, n),
+              "Phi": (batch, N * nx, nx), "xbar": (batch, N * nx)}
+    out = _alloc({k: (shapes[k], dt) for k in want if k not in out}, dev, out, keyed=True)
     rc = _lib().mpcqp_condense(
         _code(dt), batch, nx, nu, N, (nat.TV if tv else 0) | (nat.GAM_PACKED if gam_packed else 0),
-        _ptr(A), sA, _ptr(B), sB, _ptr(Q), sQ, _ptr(R), sR, _ptr(Qf), sQf, _ptr(c), sC,
-        _ptr(x0), sX, _ptr(out.get("H")), _ptr(out.get("F")), _ptr(out.get("f")),
-        _ptr(out.get("Gam")), _ptr(out.get("Phi")), _ptr(out.get("xbar")), _stream())
+        *head, *[_ptr(out.get(k)) for k in shapes], _stream())
     nat.check(rc, "mpcqp_condense")
     return {k: out[k] for k in want}
 
@@ -206,36 +348,15 @@ def mpc_box(A, B, Q, R, Qf, N: int, x0, lb=None, ub=None, c=None, *, tv: bool = 
     """Fused per-instance condense + input-box QP (include/mpcqp.h
     ``mpcqp_mpc_box``).  Same plant conventions as ``condense``; lb/ub are
     scalars, (N*nu,) shared or (b, N*nu).  Returns (z (b, N*nu), status)."""
-    dt = A.dtype if isinstance(A, torch.Tensor) else torch.float64
-    dev = A.device if isinstance(A, torch.Tensor) else torch.device("cuda")
-    A, B, Q, R, Qf = (_dev(v, dt, dev) for v in (A, B, Q, R, Qf))
-    x0, c = _dev(x0, dt, dev), _dev(c, dt, dev)
-    nx, nu = int(B.shape[-2]), int(B.shape[-1])
-    R = _weight_r(R, nu)
+    dt, dev, nx, nu, keep, insts, head = _plant(A, B, Q, R, Qf, x0, c, tv)
     n = N * nu
-    base = 3 if tv else 2
-    sA, bA = _inst(A, base, "A")
-    sB, bB = _inst(B, base, "B")
-    sQ, bQ = _inst(Q, 2, "Q")
-    sR, bR = _inst(R, 2, "R")
-    sQf, bQf = _inst(Qf, 2, "Qf")
-    sC, bC = _inst(c, 2, "c")
-    sX, bX = _inst(x0, 1, "x0")
-    lbt, slb = _bound(lb, n, dt, dev)
-    ubt, sub = _bound(ub, n, dt, dev)
-    batch = _batch_of((sA, bA), (sB, bB), (sQ, bQ), (sR, bR), (sQf, bQf), (sC, bC), (sX, bX),
-                      (slb, lbt.shape[0] if lbt is not None and lbt.ndim == 2 else None),
-                      (sub, ubt.shape[0] if ubt is not None and ubt.ndim == 2 else None))
-    if out is None:
-        z = torch.empty((batch, n), dtype=dt, device=dev)
-        status = torch.empty((batch,), dtype=torch.int32, device=dev)
-    else:
-        z, status = out
+    lbt, slb, blb = _bound(lb, n, dt, dev)
+    ubt, sub, bub = _bound(ub, n, dt, dev)
+    batch = _batch_of(*insts, (slb, blb), (sub, bub))
+    z, status = _alloc({"z": ((batch, n), dt), "status": ((batch,), torch.int32)}, dev, out)
     rc = _lib().mpcqp_mpc_box(
-        _code(dt), batch, nx, nu, N, nat.TV if tv else 0,
-        _ptr(A), sA, _ptr(B), sB, _ptr(Q), sQ, _ptr(R), sR, _ptr(Qf), sQf, _ptr(c), sC,
-        _ptr(x0), sX, _ptr(lbt), slb, _ptr(ubt), sub, _ptr(z), _ptr(status), int(max_iter),
-        float(tol), _stream())
+        _code(dt), batch, nx, nu, N, nat.TV if tv else 0, *head, _ptr(lbt), slb, _ptr(ubt), sub,
+        _ptr(z), _ptr(status), int(max_iter), float(tol), _stream())
     nat.check(rc, "mpcqp_mpc_box")
     return z, status
 
@@ -251,23 +372,10 @@ def _mpc_step_args(A, B, Q, R, Qf, N, x0, xlo, xhi, lb, ub, c, tv):
     """Normalise the arguments shared by mpc_qp / mpc_ipm (plant conventions
     of ``condense``; state bounds (nx,) repeated over the horizon, (N*nx,)
     shared or (b, N*nx); input bounds as ``mpc_box``)."""
-    dt = A.dtype if isinstance(A, torch.Tensor) else torch.float64
-    dev = A.device if isinstance(A, torch.Tensor) else torch.device("cuda")
-    A, B, Q, R, Qf = (_dev(v, dt, dev) for v in (A, B, Q, R, Qf))
-    x0, c = _dev(x0, dt, dev), _dev(c, dt, dev)
-    nx, nu = int(B.shape[-2]), int(B.shape[-1])
-    R = _weight_r(R, nu)
+    dt, dev, nx, nu, keep, insts, head = _plant(A, B, Q, R, Qf, x0, c, tv)
     n, m = N * nu, N * nx
-    base = 3 if tv else 2
-    sA, bA = _inst(A, base, "A")
-    sB, bB = _inst(B, base, "B")
-    sQ, bQ = _inst(Q, 2, "Q")
-    sR, bR = _inst(R, 2, "R")
-    sQf, bQf = _inst(Qf, 2, "Qf")
-    sC, bC = _inst(c, 2, "c")
-    sX, bX = _inst(x0, 1, "x0")
 
-    def sbound(v):
+    def sbound(v, _):
         if v is None:
             return None, 0, None
         t = _dev(v, dt, dev)
@@ -278,22 +386,14 @@ def _mpc_step_args(A, B, Q, R, Qf, N, x0, xlo, xhi, lb, ub, c, tv):
             raise ValueError(f"state bounds need {m} (= N*nx) entries, got {tuple(t.shape)}")
         return t, s, bb
 
-    xlo_t, sxl, bxl = sbound(xlo)
-    xhi_t, sxh, bxh = sbound(xhi)
-    if xlo_t is not None and xhi_t is not None and sxl != sxh:
-        raise ValueError("xlo and xhi must both be shared or both per instance")
-    sXb = max(sxl, sxh)
-    lbt, slb = _bound(lb, n, dt, dev)
-    ubt, sub = _bound(ub, n, dt, dev)
-    batch = _batch_of((sA, bA), (sB, bB), (sQ, bQ), (sR, bR), (sQf, bQf), (sC, bC), (sX, bX),
-                      (sxl, bxl), (sxh, bxh),
-                      (slb, lbt.shape[0] if lbt is not None and lbt.ndim == 2 else None),
-                      (sub, ubt.shape[0] if ubt is not None and ubt.ndim == 2 else None))
+    xlo_t, xhi_t, sXb, bxl, bxh = _row_pair(
+        xlo, xhi, "raise", sbound, "xlo and xhi must both be shared or both per instance")
+    lbt, slb, blb = _bound(lb, n, dt, dev)
+    ubt, sub, bub = _bound(ub, n, dt, dev)
+    batch = _batch_of(*insts, (sXb, bxl), (sXb, bxh), (slb, blb), (sub, bub))
     return dict(dt=dt, dev=dev, nx=nx, nu=nu, n=n, m=m, batch=batch,
-                head=(_ptr(A), sA, _ptr(B), sB, _ptr(Q), sQ, _ptr(R), sR, _ptr(Qf), sQf,
-                      _ptr(c), sC, _ptr(x0), sX, _ptr(xlo_t), _ptr(xhi_t), sXb,
-                      _ptr(lbt), slb, _ptr(ubt), sub),
-                keep=(A, B, Q, R, Qf, c, x0, xlo_t, xhi_t, lbt, ubt),
+                head=(*head, _ptr(xlo_t), _ptr(xhi_t), sXb, _ptr(lbt), slb, _ptr(ubt), sub),
+                keep=(keep, xlo_t, xhi_t, lbt, ubt),
                 sbox=xlo_t is not None or xhi_t is not None)
 
 
@@ -313,14 +413,11 @@ def mpc_qp(A, B, Q, R, Qf, N: int, x0, xlo=None, xhi=None, lb=None, ub=None, c=N
     g = _mpc_step_args(A, B, Q, R, Qf, N, x0, xlo, xhi, lb, ub, c, tv)
     dt, dev, batch, n, m, nx = g["dt"], g["dev"], g["batch"], g["n"], g["m"], g["nx"]
     sbox = g["sbox"]
-    if out is None:
-        z = torch.empty((batch, n), dtype=dt, device=dev)
-        y = torch.empty((batch, m), dtype=dt, device=dev) if sbox else None
-        status = torch.empty((batch,), dtype=torch.int32, device=dev)
-        X = torch.empty((batch, N, nx), dtype=dt, device=dev) if states else None
-    else:
-        z, y, status = out[:3]
-        X = out[3] if len(out) > 3 else None
+    o = _alloc({"z": ((batch, n), dt), "y": ((batch, m), dt) if sbox else None,
+                "status": ((batch,), torch.int32), "X": ((batch, N, nx), dt) if states else None},
+               dev, out)
+    z, y, status = o[:3]
+    X = o[3] if len(o) > 3 else None
     lib = _lib()
     wsb = int(lib.mpcqp_mpc_qp_workspace(_code(dt), batch, nx, g["nu"], N, int(sbox)))
     ws = _workspace(wsb, dev, ws)
@@ -353,12 +450,9 @@ def mpc_ipm(A, B, Q, R, Qf, N: int, x0, xlo=None, xhi=None, lb=None, ub=None, c=
     n2 = nx + g["nu"]
     H2t = None if H2 is None else _dev(H2, dt, dev).reshape(batch, N * n2 * n2)
     q2t = None if q2 is None else _dev(q2, dt, dev).reshape(batch, N * n2)
-    o = dict(out or {})
-    shapes = dict(z=((batch, n), dt), y=((batch, m), dt), lam_u=((batch, n), dt),
-                  X=((batch, N, nx), dt), pi=((batch, N, nx), dt), status=((batch,), torch.int32))
-    for k, (shp, kd) in shapes.items():
-        if k not in o:
-            o[k] = torch.empty(shp, dtype=kd, device=dev)
+    o = _alloc(dict(z=((batch, n), dt), y=((batch, m), dt), lam_u=((batch, n), dt),
+                    X=((batch, N, nx), dt), pi=((batch, N, nx), dt),
+                    status=((batch,), torch.int32)), dev, out, keyed=True)
     lib = _lib()
     wsb = int(lib.mpcqp_mpc_ipm_workspace(_code(dt), batch, nx, g["nu"], N))
     ws = _workspace(wsb, dev, ws)
@@ -398,8 +492,7 @@ def mpc_box_loop(A, B, Q, R, Qf, N: int, x0, lb=None, ub=None, steps: int = 1, *
     (steps, b, nx) is a plant disturbance, x_{t+1} = A x_t + B u_t + w_t.
     ``cold`` starts every step from the empty active set.  With any of these
     the call goes to ``mpcqp_mpc_box_loop_affine``."""
-    dt = A.dtype if isinstance(A, torch.Tensor) else torch.float64
-    dev = A.device if isinstance(A, torch.Tensor) else torch.device("cuda")
+    dt, dev = _dt_dev(A)
     A, B = _dev(A, dt, dev), _dev(B, dt, dev)
     x0 = _dev(x0, dt, dev)
     nx, nu = int(B.shape[-2]), int(B.shape[-1])
@@ -414,16 +507,13 @@ def mpc_box_loop(A, B, Q, R, Qf, N: int, x0, lb=None, ub=None, steps: int = 1, *
     if tracking and "Gam" not in cd:
         cd["Gam"] = condense(A, B, Q, R, Qf, N, outputs=("Gam",))["Gam"]
     H, F = cd["H"], cd["F"]
-    sH, _ = _inst(H, 1, "H")
-    sF, _ = _inst(F, 2, "F")
-    if H.ndim == 2 and H.shape[0] == 1:   # a shared plant condenses to one instance
-        sH = 0
-    if F.ndim == 3 and F.shape[0] == 1:
-        sF = 0
+    # H and F with a leading 1 are shared whatever the batch; A and B are taken as given
+    sH, _ = _inst_one(H, 1, "H")
+    sF, _ = _inst_one(F, 2, "F")
     sA, _ = _inst(A, 2, "A")
     sB, _ = _inst(B, 2, "B")
-    lbt, slb = _bound(lb, n, dt, dev)
-    ubt, sub = _bound(ub, n, dt, dev)
+    lbt, slb, _ = _bound(lb, n, dt, dev)
+    ubt, sub, _ = _bound(ub, n, dt, dev)
     if tracking:
         Gam = cd["Gam"]
         if Gam.ndim == 3 and Gam.shape[0] == 1:
@@ -435,55 +525,28 @@ def mpc_box_loop(A, B, Q, R, Qf, N: int, x0, lb=None, ub=None, steps: int = 1, *
         raise ValueError(f"g must be ({T}, {n}) or ({T}, {batch}, {n}), got {tuple(g.shape)}")
     if w is not None and tuple(w.shape) != (T, batch, nx):
         raise ValueError(f"w must be ({T}, {batch}, {nx}), got {tuple(w.shape)}")
-    o = dict(out or {})
-    shapes = dict(xs=((T + 1, batch, nx), dt), us=((T, batch, nu), dt),
-                  status=((T, batch), torch.int32))
+    spec = dict(xs=((T + 1, batch, nx), dt), us=((T, batch, nu), dt),
+                status=((T, batch), torch.int32))
     if plans:
-        shapes["zs"] = ((T, batch, n), dt)
-    for k, (shp, kd) in shapes.items():
-        if k not in o:
-            o[k] = torch.empty(shp, dtype=kd, device=dev)
+        spec["zs"] = ((T, batch, n), dt)
+    o = _alloc(spec, dev, out, keyed=True)
+    dims = (_code(dt), batch, nx, nu, N, T)
+    head = (_ptr(H), sH, _ptr(F), sF, _ptr(A), sA, _ptr(B), sB, _ptr(x0), nx, _ptr(lbt), slb,
+            _ptr(ubt), sub)
+    tail = (_ptr(o["xs"]), _ptr(o["us"]), _ptr(o.get("zs")), _ptr(o["status"]), int(max_iter),
+            float(tol), _stream())
     if g is not None or w is not None or cold:
         rc = _lib().mpcqp_mpc_box_loop_affine(
-            _code(dt), batch, nx, nu, N, T, nat.LOOP_COLD if cold else 0, _ptr(H), sH, _ptr(F), sF,
-            _ptr(A), sA, _ptr(B), sB, _ptr(x0), nx, _ptr(lbt), slb, _ptr(ubt), sub,
-            _ptr(g), 0 if g is None or g.ndim == 2 else n, _ptr(w),
-            _ptr(o["xs"]), _ptr(o["us"]), _ptr(o.get("zs")), _ptr(o["status"]), int(max_iter),
-            float(tol), _stream())
+            *dims, nat.LOOP_COLD if cold else 0, *head,
+            _ptr(g), 0 if g is None or g.ndim == 2 else n, _ptr(w), *tail)
         nat.check(rc, "mpcqp_mpc_box_loop_affine")
         return o
-    rc = _lib().mpcqp_mpc_box_loop(_code(dt), batch, nx, nu, N, T, _ptr(H), sH, _ptr(F), sF,
-                                   _ptr(A), sA, _ptr(B), sB, _ptr(x0), nx, _ptr(lbt), slb,
-                                   _ptr(ubt), sub, _ptr(o["xs"]), _ptr(o["us"]), _ptr(o.get("zs")),
-                                   _ptr(o["status"]), int(max_iter), float(tol), _stream())
+    rc = _lib().mpcqp_mpc_box_loop(*dims, *head, *tail)
     nat.check(rc, "mpcqp_mpc_box_loop")
     return o
 
 
-def _weight_r(R, nu: int):
-    """R as (nu, nu) (or batched).  FHC.py:141 passes R with shape (1,), which
-    NumPy broadcasts; a 1-D R is accepted only for nu == 1 (shape (1,)) -- a
-    vector of diagonal weights must be given as a matrix (torch.diag)."""
-    if R.ndim == 1:
-        if R.shape[0] != 1 or nu != 1:
-            raise ValueError(f"R of shape {tuple(R.shape)} with nu={nu}: pass an (nu, nu) matrix")
-        return R.reshape(1, 1).contiguous()
-    return R
-
-
 # ----------------------------------------------------------------- box QP
-def _bound(v, n, dt, dev):
-    if v is None:
-        return None, 0
-    if not isinstance(v, torch.Tensor) and (isinstance(v, (int, float))):
-        return torch.full((n,), float(v), dtype=dt, device=dev), 0
-    t = _dev(v, dt, dev)
-    if t.ndim == 0:
-        return t.expand(n).contiguous(), 0
-    s, _ = _inst(t, 1, "bound")
-    return t, s
-
-
 def solve_box(H, f, lb=None, ub=None, *, max_iter: int = 0, tol: float = 0.0,
               out: tuple | None = None, presweep: bool = True, ws: torch.Tensor | None = None):
     """Batched  min 1/2 z'Hz + f'z  s.t.  lb <= z <= ub.  Returns (z, status).
@@ -499,16 +562,10 @@ def solve_box(H, f, lb=None, ub=None, *, max_iter: int = 0, tol: float = 0.0,
         raise ValueError(f"H must be packed lower with {n * (n + 1) // 2} entries, got {tuple(H.shape)}")
     sH, bH = _inst(H, 1, "H")
     sf, bf = _inst(f, 1, "f")
-    lbt, slb = _bound(lb, n, dt, dev)
-    ubt, sub = _bound(ub, n, dt, dev)
-    batch = _batch_of((sH, bH), (sf, bf),
-                      (slb, lbt.shape[0] if lbt is not None and lbt.ndim == 2 else None),
-                      (sub, ubt.shape[0] if ubt is not None and ubt.ndim == 2 else None))
-    if out is None:
-        z = torch.empty((batch, n), dtype=dt, device=dev)
-        status = torch.empty((batch,), dtype=torch.int32, device=dev)
-    else:
-        z, status = out
+    lbt, slb, blb = _bound(lb, n, dt, dev)
+    ubt, sub, bub = _bound(ub, n, dt, dev)
+    batch = _batch_of((sH, bH), (sf, bf), (slb, blb), (sub, bub))
+    z, status = _alloc({"z": ((batch, n), dt), "status": ((batch,), torch.int32)}, dev, out)
     lib = _lib()
     wsb = int(lib.mpcqp_solve_qp_workspace(_code(dt), batch, n, 0)) if presweep else 0
     ws = _workspace(wsb, dev, ws)
@@ -529,14 +586,12 @@ def _vjp_common(lb, ub, n, dt, dev, batch, insts, status, status_shape):
     forward's status.  Returns ``(lbt, slb, ubt, sub, status, shared)`` where
     ``shared(g, stride, ref=None)`` is the epilogue of a gradient: summed over
     the batch where the input is shared (stride 0), in the shape of ``ref``."""
-    lbt, slb = _bound(lb, n, dt, dev)
-    ubt, sub = _bound(ub, n, dt, dev)
+    lbt, slb, blb = _bound(lb, n, dt, dev)
+    ubt, sub, bub = _bound(ub, n, dt, dev)
     for name, t in (("lb", lbt), ("ub", ubt)):
         if t is not None and t.shape[-1] != n:
             raise ValueError(f"{name}: last dimension {t.shape[-1]} != n = {n}")
-    _batch_of((1, batch), *insts,
-              (slb, lbt.shape[0] if lbt is not None and lbt.ndim == 2 else None),
-              (sub, ubt.shape[0] if ubt is not None and ubt.ndim == 2 else None))
+    _batch_of((1, batch), *insts, (slb, blb), (sub, bub))
     if status is not None:
         if status.dtype != torch.int32 or tuple(status.shape) != status_shape or status.device != dev:
             what = "(batch,)" if len(status_shape) == 1 else "(T, batch)"
@@ -581,11 +636,10 @@ def solve_box_vjp(H, z, lb, ub, gz, *, status=None, need_H: bool = True) -> dict
     sH, bH = _inst(H, 1, "H")
     lbt, slb, ubt, sub, status, shared = _vjp_common(lb, ub, n, dt, dev, batch, [(sH, bH)],
                                                      status, (batch,))
-    gf = torch.empty((batch, n), dtype=dt, device=dev)
-    glb = torch.empty((batch, n), dtype=dt, device=dev)
-    gub = torch.empty((batch, n), dtype=dt, device=dev)
-    gH = torch.empty((batch, n * (n + 1) // 2), dtype=dt, device=dev) if need_H else None
-    vstatus = torch.empty((batch,), dtype=torch.int32, device=dev)
+    gf, glb, gub, gH, vstatus = _alloc(
+        {"gf": ((batch, n), dt), "glb": ((batch, n), dt), "gub": ((batch, n), dt),
+         "gH": ((batch, n * (n + 1) // 2), dt) if need_H else None,
+         "vstatus": ((batch,), torch.int32)}, dev)
     rc = _lib().mpcqp_solve_box_vjp(_code(dt), batch, n, _ptr(H), sH, _ptr(z), _ptr(lbt), slb,
                                     _ptr(ubt), sub, _ptr(status), _ptr(gz), _ptr(gf), _ptr(glb),
                                     _ptr(gub), _ptr(gH), _ptr(vstatus), _stream())
@@ -633,16 +687,10 @@ def mpc_box_loop_vjp(H, F, A, B, lb, ub, xs, zs, gxs=None, gus=None, gzs=None, *
     if unknown:
         raise ValueError(f"need: unknown outputs {sorted(unknown)}")
 
-    def inst(t, base, name):
-        s, bt = _inst(t, base, name)
-        if bt == 1 and batch > 1:   # a shared plant condenses to one instance
-            s, bt = 0, None
-        return s, bt
-
-    sH, bH = inst(H, 1, "H")
-    sF, bF = inst(F, 2, "F")
-    sA, bA = inst(A, 2, "A")
-    sB, bB = inst(B, 2, "B")
+    # a leading 1 of H, F, A or B is shared, unless the batch itself is 1
+    (sH, bH), (sF, bF), (sA, bA), (sB, bB) = (
+        _inst_one(t, nd, name, batch > 1) for t, nd, name in ((H, 1, "H"), (F, 2, "F"),
+                                                              (A, 2, "A"), (B, 2, "B")))
     lbt, slb, ubt, sub, status, shared = _vjp_common(
         lb, ub, n, dt, dev, batch, [(sH, bH), (sF, bF), (sA, bA), (sB, bB)], status, (T, batch))
     ups = {}
@@ -655,26 +703,24 @@ def mpc_box_loop_vjp(H, F, A, B, lb, ub, xs, zs, gxs=None, gus=None, gzs=None, *
     shapes = dict(gx0=(batch, nx), gH=(batch, n * (n + 1) // 2), gF=(batch, n, nx),
                   gA=(batch, nx, nx), gB=(batch, nx, nu), glb=(batch, n), gub=(batch, n),
                   gg=(T, batch, n), gw=(T, batch, nx))
-    o = {k: (torch.empty(shapes[k], dtype=dt, device=dev) if k in need else None)
-         for k in LOOP_VJP_OUTPUTS}
-    vstatus = torch.empty((batch,), dtype=torch.int32, device=dev)
+    spec = {k: (shapes[k], dt) if k in need else None for k in LOOP_VJP_OUTPUTS}
+    o = _alloc({**spec, "vstatus": ((batch,), torch.int32)}, dev, keyed=True)
     rc = _lib().mpcqp_mpc_box_loop_vjp(
         _code(dt), batch, nx, nu, n // nu, T, _ptr(H), sH, _ptr(F), sF, _ptr(A), sA, _ptr(B), sB,
         _ptr(lbt), slb, _ptr(ubt), sub, _ptr(xs), _ptr(zs), _ptr(status), _ptr(ups["gxs"]),
         _ptr(ups["gus"]), _ptr(ups["gzs"]), *(_ptr(o[k]) for k in LOOP_VJP_OUTPUTS),
-        _ptr(vstatus), _stream())
+        _ptr(o["vstatus"]), _stream())
     nat.check(rc, "mpcqp_mpc_box_loop_vjp")
     for k, s, ref in (("gH", sH, H), ("gF", sF, F), ("gA", sA, A), ("gB", sB, B),
                       ("glb", slb, None), ("gub", sub, None)):
         o[k] = shared(o[k], s, ref)
-    o["vstatus"] = vstatus
     return o
 
 
 # ------------------------------------------------------------- polytope QP
 def _poly_box(v, n, dt, dev, name):
     """lbz / ubz of the polytope QP: shared by the batch, a scalar or (n,)."""
-    t, _ = _bound(v, n, dt, dev)
+    t = _bound(v, n, dt, dev)[0]
     if t is not None and tuple(t.shape) != (n,):
         raise ValueError(f"{name} must be a scalar or ({n},), got {tuple(t.shape)}")
     return t
@@ -684,35 +730,27 @@ def _poly_vec(t, width, name):
     """(stride, batch) of a (width,) shared or (batch, width) per-instance operand."""
     if t is None:
         return 0, None
-    if t.ndim not in (1, 2) or t.shape[-1] != width:
-        raise ValueError(f"{name} must be ({width},) or (batch, {width}), got {tuple(t.shape)}")
-    return (width, int(t.shape[0])) if t.ndim == 2 else (0, None)
+    shape = t.shape
+    if len(shape) not in (1, 2) or shape[-1] != width:
+        raise ValueError(f"{name} must be ({width},) or (batch, {width}), got {tuple(shape)}")
+    return (width, int(shape[0])) if len(shape) == 2 else (0, None)
 
 
 def _poly_rows(hl, hu, m):
     """(stride, batch) of the row bounds: both shared or both per instance."""
-    (sl, bl), (su, bu) = _poly_vec(hl, m, "hl"), _poly_vec(hu, m, "hu")
-    if hl is not None and hu is not None and hl.ndim != hu.ndim:
-        raise ValueError("hl and hu must both be shared or both per instance, got "
-                         f"{tuple(hl.shape)} and {tuple(hu.shape)}")
+    _, _, sh, bl, bu = _row_pair(
+        hl, hu, "raise", lambda t, k: (t, *_poly_vec(t, m, ("hl", "hu")[k])),
+        "hl and hu must both be shared or both per instance, got {lo} and {hi}")
     if bl is not None and bu is not None and bl != bu:
         raise ValueError(f"hl and hu have different batch sizes {bl} and {bu}")
-    return max(sl, su), bl if bl is not None else bu
+    return sh, bl if bl is not None else bu
 
 
 def _poly_out(out, batch, n, mt, dt, dev):
     """z, y, status of a polytope solve: allocated, or the checked ``out``
     triple (contiguous, of dtype ``dt`` on the operands' device ``dev``)."""
-    shapes = (("z", (batch, n), dt), ("y", (batch, mt), dt), ("status", (batch,), torch.int32))
-    if out is None:
-        return tuple(torch.empty(shp, dtype=kd, device=dev) for _, shp, kd in shapes)
-    if not isinstance(out, (tuple, list)) or len(out) != 3:
-        raise ValueError("out must be a triple (z, y, status)")
-    for t, (name, shp, kd) in zip(out, shapes):
-        if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shp or t.dtype != kd
-                or t.device != dev or not t.is_contiguous()):
-            raise ValueError(f"out {name} must be a contiguous {kd} tensor of shape {shp} on {dev}")
-    return tuple(out)
+    return _alloc({"z": ((batch, n), dt), "y": ((batch, mt), dt),
+                   "status": ((batch,), torch.int32)}, dev, out, check=True)
 
 
 def solve_poly(H, f, G=None, hl=None, hu=None, lbz=None, ubz=None, *, max_iter: int = 0,
@@ -874,15 +912,17 @@ class PolyQP:
         if T < 0:
             raise ValueError(f"steps={T} < 0")
         hl, hu = _dev(hl, dt, dev), _dev(hu, dt, dev)
-        sh = 0
-        for name, h in (("hl", hl), ("hu", hu)):
+
+        def side(h, k):
             if h is None:
-                continue
+                return None, 0, None
             if h.shape[-1] != m or h.ndim not in (1, 2) or (h.ndim == 2 and h.shape[0] != batch):
-                raise ValueError(f"{name} must be ({m},) or ({batch}, {m}), got {tuple(h.shape)}")
-            sh = max(sh, m if h.ndim == 2 else 0)
-        if hl is not None and hu is not None and hl.ndim != hu.ndim:
-            raise ValueError("hl and hu must both be shared or both per instance")
+                raise ValueError(f"{('hl', 'hu')[k]} must be ({m},) or ({batch}, {m}), got "
+                                 f"{tuple(h.shape)}")
+            return (h, m, batch) if h.ndim == 2 else (h, 0, None)
+
+        sh = _row_pair(hl, hu, "raise", side,
+                       "hl and hu must both be shared or both per instance")[2]
         E = _dev(E, dt, dev)
         if E is not None and tuple(E.shape) != (m, nx):
             raise ValueError(f"E must be ({m}, {nx}), got {tuple(E.shape)}")
@@ -921,49 +961,36 @@ class PolyQP:
                                  f"on {dev}")
             else:
                 sb = int(scratch.numel())
-        shapes = dict(xs=((T + 1, batch, nx), dt), us=((T, batch, nu), dt),
-                      status=((T, batch), torch.int32))
+        spec = dict(xs=((T + 1, batch, nx), dt), us=((T, batch, nu), dt),
+                    status=((T, batch), torch.int32))
         if slacks:
-            shapes["eps"] = ((T, batch, m), dt)
+            spec["eps"] = ((T, batch, m), dt)
         if plans:
-            shapes["zs"] = ((T, batch, n), dt)
+            spec["zs"] = ((T, batch, n), dt)
         if multipliers:
-            shapes["ys"] = ((T, batch, self.mt), dt)
-        for k, (shp, kd) in shapes.items():
-            if k not in o:
-                o[k] = torch.empty(shp, dtype=kd, device=dev)
-            elif tuple(o[k].shape) != shp or o[k].dtype != kd or not o[k].is_contiguous():
-                raise ValueError(f"out[{k!r}] must be a contiguous {kd} tensor of shape {shp}")
+            spec["ys"] = ((T, batch, self.mt), dt)
+        o = _alloc(spec, dev, o, keyed=True, check=True)
+        head = (_code(dt), batch, n, m, self.nbox, nx, nu, T, nat.LOOP_COLD if cold else 0,
+                _ptr(self.ws), _ptr(E), _ptr(A), _ptr(B), _ptr(x0), nx, _ptr(hl), _ptr(hu), sh,
+                _ptr(self.lbz), _ptr(self.ubz), _ptr(w))
+        outs = (_ptr(o["xs"]), _ptr(o["us"]), _ptr(o.get("zs")), _ptr(o.get("ys")))
+        tail = (_ptr(o["status"]), int(max_iter), float(tol), _stream())
+        eps = _ptr(o.get("eps"))
         if g is not None or e is not None:
             if rho is None or m == 0:
                 rho = sigma = None
             rc = _lib().mpcqp_mpc_poly_loop_affine(
-                _code(dt), batch, n, m, self.nbox, nx, nu, T, nat.LOOP_COLD if cold else 0,
-                _ptr(self.ws), _ptr(E), _ptr(A), _ptr(B), _ptr(x0), nx, _ptr(hl), _ptr(hu), sh,
-                _ptr(self.lbz), _ptr(self.ubz), _ptr(w), _ptr(rho), _ptr(sigma),
-                _ptr(g), 0 if g is None or g.ndim == 2 else n,
-                _ptr(e), 0 if e is None or e.ndim == 2 else m, _ptr(scratch), sb,
-                _ptr(o["xs"]), _ptr(o["us"]), _ptr(o.get("zs")), _ptr(o.get("ys")),
-                _ptr(o.get("eps")), _ptr(o["status"]), int(max_iter), float(tol), _stream())
+                *head, _ptr(rho), _ptr(sigma), _ptr(g), 0 if g is None or g.ndim == 2 else n,
+                _ptr(e), 0 if e is None or e.ndim == 2 else m, _ptr(scratch), sb, *outs, eps, *tail)
             nat.check(rc, "mpcqp_mpc_poly_loop_affine")
             if scratch is not None:
                 o["scratch"] = scratch
             return o
         if rho is not None and m > 0:
-            rc = _lib().mpcqp_mpc_poly_loop_soft(
-                _code(dt), batch, n, m, self.nbox, nx, nu, T, nat.LOOP_COLD if cold else 0,
-                _ptr(self.ws), _ptr(E), _ptr(A), _ptr(B), _ptr(x0), nx, _ptr(hl), _ptr(hu), sh,
-                _ptr(self.lbz), _ptr(self.ubz), _ptr(w), _ptr(rho), _ptr(sigma), _ptr(o["xs"]),
-                _ptr(o["us"]), _ptr(o.get("zs")), _ptr(o.get("ys")), _ptr(o.get("eps")),
-                _ptr(o["status"]), int(max_iter), float(tol), _stream())
+            rc = _lib().mpcqp_mpc_poly_loop_soft(*head, _ptr(rho), _ptr(sigma), *outs, eps, *tail)
             nat.check(rc, "mpcqp_mpc_poly_loop_soft")
             return o
-        rc = _lib().mpcqp_mpc_poly_loop(
-            _code(dt), batch, n, m, self.nbox, nx, nu, T, nat.LOOP_COLD if cold else 0,
-            _ptr(self.ws), _ptr(E), _ptr(A), _ptr(B), _ptr(x0), nx, _ptr(hl), _ptr(hu), sh,
-            _ptr(self.lbz), _ptr(self.ubz), _ptr(w), _ptr(o["xs"]), _ptr(o["us"]),
-            _ptr(o.get("zs")), _ptr(o.get("ys")), _ptr(o["status"]), int(max_iter), float(tol),
-            _stream())
+        rc = _lib().mpcqp_mpc_poly_loop(*head, *outs, *tail)
         nat.check(rc, "mpcqp_mpc_poly_loop")
         return o
 
@@ -1045,8 +1072,7 @@ def mpc_poly_loop(A, B, Q, R, Qf, N: int, x0, xlo=None, xhi=None, lb=None, ub=No
     unbatched).  ``x_ref`` / ``u_ref`` (shapes of ``tracking_terms``) make
     the cost track a reference trajectory with preview instead of the origin;
     the state and input boxes stay boxes on x and u."""
-    dt = A.dtype if isinstance(A, torch.Tensor) else torch.float64
-    dev = A.device if isinstance(A, torch.Tensor) else torch.device("cuda")
+    dt, dev = _dt_dev(A)
     A, B = _dev(A, dt, dev), _dev(B, dt, dev)
     if A.ndim != 2 or B.ndim != 2:
         raise ValueError("mpc_poly_loop: the model (A, B) is shared by the batch")
@@ -1116,23 +1142,13 @@ def solve_qp(H, f, G=None, hl=None, hu=None, lb=None, ub=None, *, max_iter: int 
     sG, bG = (0, None) if G is None else _inst(G, 2, "G")
     hl = _dev(hl, dt, dev)
     hu = _dev(hu, dt, dev)
-    if hl is not None and hu is not None and hl.shape != hu.shape:
-        raise ValueError("hl and hu must have the same shape")
-    sh, bh = 0, None
-    for h in (hl, hu):
-        if h is not None:
-            sh, bh = _inst(h, 1, "h")
-    lbt, slb = _bound(lb, n, dt, dev)
-    ubt, sub = _bound(ub, n, dt, dev)
-    batch = _batch_of((sH, bH), (sf, bf), (sG, bG), (sh, bh),
-                      (slb, lbt.shape[0] if lbt is not None and lbt.ndim == 2 else None),
-                      (sub, ubt.shape[0] if ubt is not None and ubt.ndim == 2 else None))
-    if out is None:
-        z = torch.empty((batch, n), dtype=dt, device=dev)
-        y = torch.empty((batch, m), dtype=dt, device=dev) if m else None
-        status = torch.empty((batch,), dtype=torch.int32, device=dev)
-    else:
-        z, y, status = out
+    _, _, sh, bhl, bhu = _row_pair(hl, hu, "equal", lambda t, _: (t, *_inst(t, 1, "h")),
+                                   "hl and hu must have the same shape")
+    lbt, slb, blb = _bound(lb, n, dt, dev)
+    ubt, sub, bub = _bound(ub, n, dt, dev)
+    batch = _batch_of((sH, bH), (sf, bf), (sG, bG), (sh, bhl), (sh, bhu), (slb, blb), (sub, bub))
+    z, y, status = _alloc({"z": ((batch, n), dt), "y": ((batch, m), dt) if m else None,
+                           "status": ((batch,), torch.int32)}, dev, out)
     lib = _lib()
     wsb = int(lib.mpcqp_solve_qp_workspace(_code(dt), batch, n, m)) if presweep else 0
     ws = _workspace(wsb, dev, ws)
@@ -1216,20 +1232,13 @@ def bicycle_rti(x0, U, params, ts: float, *, states: bool = False):
     x0 = x0.contiguous()
     U = U.contiguous()
     b, N = int(U.shape[0]), int(U.shape[1])
-    A = torch.empty((b, N, 4, 4), dtype=dt, device=dev)
-    B = torch.empty((b, N, 4, 2), dtype=dt, device=dev)
-    c = torch.empty((b, N, 4), dtype=dt, device=dev)
-    X = torch.empty((b, N + 1, 4), dtype=dt, device=dev) if states else None
+    A, B, c, X = _alloc({"A": ((b, N, 4, 4), dt), "B": ((b, N, 4, 2), dt), "c": ((b, N, 4), dt),
+                         "X": ((b, N + 1, 4), dt) if states else None}, dev)
     prm = _bike_params(params)
     rc = _lib().mpcqp_bicycle_rti(_code(dt), b, N, float(ts), prm, _ptr(x0), 4, _ptr(U), 2 * N,
                                   _ptr(X), _ptr(A), _ptr(B), _ptr(c), _stream())
     nat.check(rc, "mpcqp_bicycle_rti")
     return (A, B, c, X) if states else (A, B, c)
-
-
-def _bike_params(params):
-    return (ctypes.c_double * 4)(params.axis_front, params.axis_rear, params.acceleration,
-                                 params.friction)
 
 
 def bicycle_hessian(X, U, pi, params, ts: float, flags=None, mu=None,
@@ -1245,42 +1254,20 @@ def bicycle_hessian(X, U, pi, params, ts: float, flags=None, mu=None,
     bicycle_sqp_step) get a proximal term on their diagonal.  integrator:
     the prediction model (0 forward Euler, 1 RK4)."""
     b, N = int(U.shape[0]), int(U.shape[1])
-    if out is None:
-        H2 = torch.empty((b, N, 6, 6), dtype=torch.float64, device=U.device)
-        q2 = torch.empty((b, N, 6), dtype=torch.float64, device=U.device)
-    else:
-        H2, q2 = out
+    H2, q2 = _alloc({"H2": ((b, N, 6, 6), torch.float64), "q2": ((b, N, 6), torch.float64)},
+                    U.device, out)
+    head = (nat.F64, b, N, float(ts), _bike_params(params), int(integrator), _ptr(X), _ptr(U),
+            _ptr(pi), _ptr(flags), _ptr(mu), _ptr(fix))
+    tail = (_ptr(H2), _ptr(q2), _stream())
     if Q is not None:
         Qc = Q.to(torch.float64).contiguous()
         Rc = R.to(torch.float64).contiguous()
-        rc = _lib().mpcqp_bicycle_hessian_convex(nat.F64, b, N, float(ts), _bike_params(params),
-                                                 int(integrator), _ptr(X), _ptr(U), _ptr(pi), _ptr(flags), _ptr(mu),
-                                                 _ptr(fix), _ptr(Qc), _ptr(Rc), float(eps), _ptr(H2),
-                                                 _ptr(q2), _stream())
+        rc = _lib().mpcqp_bicycle_hessian_convex(*head, _ptr(Qc), _ptr(Rc), float(eps), *tail)
         nat.check(rc, "mpcqp_bicycle_hessian_convex")
         return H2, q2
-    rc = _lib().mpcqp_bicycle_hessian(nat.F64, b, N, float(ts), _bike_params(params),
-                                      int(integrator), _ptr(X),
-                                      _ptr(U), _ptr(pi), _ptr(flags), _ptr(mu), _ptr(fix), _ptr(H2),
-                                      _ptr(q2), _stream())
+    rc = _lib().mpcqp_bicycle_hessian(*head, *tail)
     nat.check(rc, "mpcqp_bicycle_hessian")
     return H2, q2
-
-
-def _bound_pair(lo, hi, b: int, width: int, what: str):
-    """A lower/upper bound pair that the C call reads with ONE instance stride:
-    each side None, (width,) shared or (b, width).  A shared side next to a
-    per-instance one is broadcast to (b, width), so the shared stride is never
-    applied to a per-instance buffer or the reverse (which would read past
-    the shared side's end).  Returns (lo, hi, stride)."""
-    sides = [v for v in (lo, hi) if v is not None]
-    for v in sides:
-        if tuple(v.shape) not in ((width,), (b, width)):
-            raise ValueError(f"{what}: shape {tuple(v.shape)} is neither ({width},) nor ({b}, {width})")
-    if not any(v.ndim == 2 for v in sides):
-        return lo, hi, 0
-    ex = lambda v: None if v is None else v.expand(b, width).contiguous()  # noqa: E731
-    return ex(lo), ex(hi), width
 
 
 def bicycle_sqp_step(x0, U, Z, yq, piq, y, pi, X, state: dict, params, ts: float, Q, R, Qf,
@@ -1298,8 +1285,7 @@ def bicycle_sqp_step(x0, U, Z, yq, piq, y, pi, X, state: dict, params, ts: float
         nat.F64, b, N, float(ts), _bike_params(params), int(integrator), _ptr(x0), 4, _ptr(Q),
         _ptr(R), _ptr(Qf),
         _ptr(xlo), _ptr(xhi), sxb, _ptr(lb), _ptr(ub), slb, _ptr(U), _ptr(Z), _ptr(yq), _ptr(piq),
-        _ptr(qp_status), _ptr(y), _ptr(pi), _ptr(X), _ptr(state["rho"]), _ptr(state["kkt"]), _ptr(state["mu"]),
-        _ptr(state["flags"]), _ptr(state.get("fix")), float(tol), _stream())
+        _ptr(qp_status), _ptr(y), _ptr(pi), _ptr(X), *_sqp_state(state), float(tol), _stream())
     nat.check(rc, "mpcqp_bicycle_sqp_step")
 
 
@@ -1319,22 +1305,18 @@ def bicycle_sqp_solve(x0, U, y, pi, X, state: dict, params, ts: float, Q, R, Qf,
     b, N = int(U.shape[0]), int(U.shape[1])
     xlo, xhi, sxb = _bound_pair(xlo, xhi, b, 4 * N, "xlo/xhi")
     lb, ub, slb = _bound_pair(lb, ub, b, 2 * N, "lb/ub")
-    for name, t, shp, dt in (("U", U, (b, N, 2), torch.float64), ("y", y, (b, N * 4), torch.float64),
-                             ("pi", pi, (b, N, 4), torch.float64),
-                             ("X", X, (b, N + 1, 4), torch.float64),
-                             ("x0", x0, (b, 4), torch.float64)):
-        if tuple(t.shape) != shp or t.dtype != dt or not t.is_contiguous() or t.device != U.device:
-            raise ValueError(f"bicycle_sqp_solve: {name} must be a contiguous {dt} device tensor "
-                             f"of shape {shp}")
+    f64 = torch.float64
+    _check_tensors("bicycle_sqp_solve", U.device,
+                   (("U", U, (b, N, 2), f64), ("y", y, (b, N * 4), f64), ("pi", pi, (b, N, 4), f64),
+                    ("X", X, (b, N + 1, 4), f64), ("x0", x0, (b, 4), f64)))
     lib = _lib()
     wsb = int(lib.mpcqp_bicycle_sqp_solve_workspace(b, N))
     ws = _workspace(wsb, U.device, ws)
     rc = lib.mpcqp_bicycle_sqp_solve(
         nat.F64, b, N, float(ts), _bike_params(params), int(integrator), nat.SQP_HESS[hessian],
         _ptr(x0), 4, _ptr(Q), _ptr(R), _ptr(Qf), _ptr(xlo), _ptr(xhi), sxb, _ptr(lb), _ptr(ub), slb,
-        _ptr(U), _ptr(y), _ptr(pi), _ptr(X), _ptr(state["rho"]), _ptr(state["kkt"]),
-        _ptr(state["mu"]), _ptr(state["flags"]), _ptr(state.get("fix")), _ptr(lam_u),
-        _ptr(qp_status), int(max_iter), int(qp_max_iter), float(tol), _ptr(ws), wsb, _stream())
+        _ptr(U), _ptr(y), _ptr(pi), _ptr(X), *_sqp_state(state), _ptr(lam_u), _ptr(qp_status),
+        int(max_iter), int(qp_max_iter), float(tol), _ptr(ws), wsb, _stream())
     nat.check(rc, "mpcqp_bicycle_sqp_solve")
     return ws
 
@@ -1354,14 +1336,12 @@ def bicycle_mpc_loop(xs, us, success, iters, state_prediction, input_prediction,
     N = int(U.shape[1])
     xlo, xhi, sxb = _bound_pair(xlo, xhi, b, 4 * N, "xlo/xhi")
     lb, ub, slb = _bound_pair(lb, ub, b, 2 * N, "lb/ub")
-    for name, t, shp, dt in (("xs", xs, (T + 1, b, 4), torch.float64), ("us", us, (T, b, 2), torch.float64),
-                             ("success", success, (T, b), torch.bool),
-                             ("iters", iters, (T, b), torch.int32),
-                             ("state_prediction", state_prediction, (T, b, N + 1, 4), torch.float64),
-                             ("input_prediction", input_prediction, (T, b, N, 2), torch.float64)):
-        if tuple(t.shape) != shp or t.dtype != dt or not t.is_contiguous() or t.device != U.device:
-            raise ValueError(f"bicycle_mpc_loop: {name} must be a contiguous {dt} device tensor "
-                             f"of shape {shp}")
+    f64 = torch.float64
+    _check_tensors("bicycle_mpc_loop", U.device,
+                   (("xs", xs, (T + 1, b, 4), f64), ("us", us, (T, b, 2), f64),
+                    ("success", success, (T, b), torch.bool), ("iters", iters, (T, b), torch.int32),
+                    ("state_prediction", state_prediction, (T, b, N + 1, 4), f64),
+                    ("input_prediction", input_prediction, (T, b, N, 2), f64)))
     lib = _lib()
     wsb = int(lib.mpcqp_bicycle_sqp_solve_workspace(b, N))
     ws = _workspace(wsb, U.device, ws)
@@ -1369,8 +1349,7 @@ def bicycle_mpc_loop(xs, us, success, iters, state_prediction, input_prediction,
         nat.F64, b, N, T, float(ts), _bike_params(params), int(integrator), nat.SQP_HESS[hessian],
         _bike_params(plant_params), int(plant), int(substeps), _ptr(Q), _ptr(R), _ptr(Qf),
         _ptr(xlo), _ptr(xhi), sxb, _ptr(lb), _ptr(ub), slb, _ptr(U), _ptr(y), _ptr(pi), _ptr(X),
-        _ptr(state["rho"]), _ptr(state["kkt"]), _ptr(state["mu"]), _ptr(state["flags"]),
-        _ptr(state.get("fix")), int(iters_first), int(iters_per_step), int(qp_max_iter), float(tol),
+        *_sqp_state(state), int(iters_first), int(iters_per_step), int(qp_max_iter), float(tol),
         float(mu0), _ptr(xs), _ptr(us), _ptr(success), _ptr(iters), _ptr(state_prediction),
         _ptr(input_prediction), _ptr(ws), wsb, _stream())
     nat.check(rc, "mpcqp_bicycle_mpc_loop")
@@ -1385,14 +1364,9 @@ def bicycle_linearise(x0, U, params, ts: float, integrator: int = 0, out: tuple 
     b, N = int(U.shape[0]), int(U.shape[1])
     dev = U.device
     x0, U = x0.contiguous(), U.contiguous()
-    if out is None:
-        f64 = dict(dtype=torch.float64, device=dev)
-        A = torch.empty((b, N, 4, 4), **f64)
-        B = torch.empty((b, N, 4, 2), **f64)
-        c = torch.empty((b, N, 4), **f64)
-        X = torch.empty((b, N + 1, 4), **f64)
-    else:
-        A, B, c, X = out
+    f64 = torch.float64
+    A, B, c, X = _alloc({"A": ((b, N, 4, 4), f64), "B": ((b, N, 4, 2), f64), "c": ((b, N, 4), f64),
+                         "X": ((b, N + 1, 4), f64)}, dev, out)
     rc = _lib().mpcqp_bicycle_linearise(nat.F64, b, N, float(ts), _bike_params(params),
                                         int(integrator), _ptr(x0), 4, _ptr(U), 2 * N, _ptr(X),
                                         _ptr(A), _ptr(B), _ptr(c), _stream())

@@ -17,6 +17,55 @@ def header_symbols():
     return sorted(set(re.findall(r"\b(mpcqp_[a-z_]+)\s*\(", txt)))
 
 
+def header_prototypes():
+    """{symbol: (return kind, [argument kinds])} of every prototype in
+    include/mpcqp.h; kinds are "ptr", "i32", "i64", "size" and "f64"."""
+    txt = open(os.path.join(ROOT, "include", "mpcqp.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = re.sub(r"//[^\n]*", "", txt)
+
+    def kind(decl):
+        decl = " ".join(decl.split())
+        if "*" in decl:
+            return "ptr"
+        words = [w for w in decl.split(" ") if w != "const"]
+        # "int batch" or a bare "int": the type is what is left without the name
+        typ = " ".join(words[:-1]) if len(words) > 1 else words[0]
+        return {"int": "i32", "int32_t": "i32", "int64_t": "i64", "size_t": "size",
+                "double": "f64"}[typ]
+
+    protos = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][\w \t]*?[\s*]+)(mpcqp_[a-z0-9_]+)\s*\(([^()]*)\)\s*;",
+                                      txt):
+        args = args.strip()
+        protos[name] = (kind(ret + " x"), [] if args in ("", "void") else
+                        [kind(a) for a in args.split(",")])
+    return protos
+
+
+def ctypes_kind(t):
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or isinstance(t, type(ctypes.POINTER(ctypes.c_int))):
+        return "ptr"
+    return {ctypes.c_int: "i32", ctypes.c_int32: "i32", ctypes.c_int64: "i64",
+            ctypes.c_size_t: "size", ctypes.c_double: "f64"}[t]
+
+
+def test_signatures_match_the_header():
+    """Return kind, argument count and every argument's kind of each entry of
+    _native.SIGNATURES against the header's prototype.  int and int32_t are one
+    kind (ctypes.c_int is c_int32); size_t is kept apart from int64_t although
+    ctypes aliases them on LP64."""
+    protos = header_prototypes()
+    assert set(protos) == set(header_symbols()) == set(nat.SIGNATURES)
+    assert len(protos) == 44
+    for name, (ret, args) in sorted(protos.items()):
+        res, argtypes = nat.SIGNATURES[name]
+        assert ctypes_kind(res) == ret, (name, "return")
+        assert len(argtypes) == len(args), name
+        for k, (t, want) in enumerate(zip(argtypes, args)):
+            assert ctypes_kind(t) == want, (name, k, t, want)
+
+
 @pytest.fixture(scope="module")
 def lib():
     return nat.load()
