@@ -17,6 +17,7 @@
 // workspace access is one fp64 per lane at consecutive addresses.
 #include <algorithm>
 #include <cstdlib>
+#include <string>
 
 #include "common.hpp"
 
@@ -27,17 +28,28 @@
 
 namespace mpcqp {
 
-template <typename T, int NX, int NU>
-__global__ __launch_bounds__(64) void ipm_kernel(ipm::Args<T> a) {
+#define MPCQP_INLINE_LAMBDA __attribute__((always_inline))
+
+// The instances of one work unit (a lane, a quad or a wave; `per` units per
+// workgroup, this one is number `unit`): instance blockIdx.x * per + unit, or
+// in list mode the entries list_begin + that, + gridDim.x * per, ... of
+// list[0 .. *list_count).  The lanes of a unit take the same entries.  f is
+// a lambda marked MPCQP_INLINE_LAMBDA: called from two places, the solver
+// would otherwise become a real function with its arrays in scratch.
+template <typename T, class F>
+__device__ __forceinline__ void ipm_for_instances(const ipm::Args<T>& a, int per, int unit, F&& f) {
+  const int first = blockIdx.x * per + unit;
   if (a.list) {
     const int cnt = *a.list_count;
-    for (int k = a.list_begin + blockIdx.x * 64 + threadIdx.x; k < cnt; k += gridDim.x * 64)
-      ipm::solve_lane<T, NX, NU>(a, a.list[k]);
+    for (int k = a.list_begin + first; k < cnt; k += gridDim.x * per) f(a.list[k]);
     return;
   }
-  const int b = blockIdx.x * 64 + threadIdx.x;
-  if (b >= a.batch) return;
-  ipm::solve_lane<T, NX, NU>(a, b);
+  if (first < a.batch) f(first);
+}
+
+template <typename T, int NX, int NU>
+__global__ __launch_bounds__(64) void ipm_kernel(ipm::Args<T> a) {
+  ipm_for_instances(a, 64, threadIdx.x, [&](int b) MPCQP_INLINE_LAMBDA { ipm::solve_lane<T, NX, NU>(a, b); });
 }
 
 // The same lane routine with the instance's workspace in LDS: G instances
@@ -50,15 +62,9 @@ __global__ __launch_bounds__(64) void ipm_lds_kernel(ipm::Args<T> a) {
   extern __shared__ __attribute__((aligned(16))) double ipm_lds[];
   const int lane = threadIdx.x;
   if (lane >= G) return;
-  if (a.list) {
-    const int cnt = *a.list_count;
-    for (int k = a.list_begin + blockIdx.x * G + lane; k < cnt; k += gridDim.x * G)
-      ipm::solve_lane<T, NX, NU, G>(a, a.list[k], ipm_lds + lane);
-    return;
-  }
-  const int b = blockIdx.x * G + lane;
-  if (b >= a.batch) return;
-  ipm::solve_lane<T, NX, NU, G>(a, b, ipm_lds + lane);
+  ipm_for_instances(a, G, lane, [&](int b) MPCQP_INLINE_LAMBDA {
+    ipm::solve_lane<T, NX, NU, G>(a, b, ipm_lds + lane);
+  });
 }
 
 // Four lanes per instance (ipm_quad.hpp), G instances per workgroup, the
@@ -68,40 +74,28 @@ __global__ __launch_bounds__(64, 1) void ipm_quad_kernel(ipm::Args<T> a) {
   extern __shared__ __attribute__((aligned(16))) double ipm_lds[];
   const int g = threadIdx.x >> 2;
   if (g >= G) return;
-  if (a.list) {
-    // the group's four lanes take the same entries (uniform trip count)
-    const int cnt = *a.list_count;
-    for (int k = a.list_begin + blockIdx.x * G + g; k < cnt; k += gridDim.x * G)
-      ipmq::solve_quad<T, G>(a, a.list[k], ipm_lds + g);
-    return;
-  }
-  const int b = blockIdx.x * G + g;
-  if (b >= a.batch) return;
-  ipmq::solve_quad<T, G>(a, b, ipm_lds + g);
+  ipm_for_instances(a, G, g, [&](int b) MPCQP_INLINE_LAMBDA {
+    ipmq::solve_quad<T, G>(a, b, ipm_lds + g);
+  });
 }
 
 // One instance per single-wave workgroup on the whole wave (ipm_wave.hpp):
 // the stage data staged one quad per stage, the per-stage work of every pass
-// on the 16 quads, the Riccati chains on quad 0.  Same iterates as
-// ipm_quad_kernel<T, 1> up to the summation order of the reductions.
+// on the 16 quads, the Riccati chains on the matrix cores.  Same iterates as
+// ipm_quad_kernel<T, 1> up to the summation order of the reductions and of
+// the matrix products.
 template <typename T>
 __global__ __launch_bounds__(64, 1) void ipm_wave_kernel(ipm::Args<T> a) {
   extern __shared__ __attribute__((aligned(16))) double ipm_lds[];
   const int lane = threadIdx.x;
   const ipmq::WsQ<1> at(ipm_lds, lane & 3);
-  auto one = [&](int b) {
+  ipm_for_instances(a, 1, 0, [&](int b) MPCQP_INLINE_LAMBDA {
     if (a.skip && (a.skip[b] & a.skip_mask)) return;
     for (int k = lane >> 2; k < a.N; k += kWave / 4) ipmq::stage_in_q(a, b, at, lane & 3, k);
     wave_lds_sync();
     ipmw::solve_wave<T>(a, b, ipm_lds);
     wave_lds_sync();
-  };
-  if (a.list) {
-    const int cnt = *a.list_count;
-    for (int k = a.list_begin + blockIdx.x; k < cnt; k += gridDim.x) one(a.list[k]);
-    return;
-  }
-  if ((int)blockIdx.x < a.batch) one((int)blockIdx.x);
+  });
 }
 
 static int64_t ipm_ldb(int batch) { return ((int64_t)batch + 63) / 64 * 64; }
@@ -145,6 +139,22 @@ bool ipm_supported(int nx, int nu) {
   return ipm_dims(nx, nu, NX, NU);
 }
 
+// Launch of a kernel with G instances' workspaces in dynamic LDS (bytes; above
+// 64 KB the kernel has to opt in), one single-wave workgroup per G instances.
+// The errors name the kernel family: "ipm_quad" or "ipm_lds".
+template <typename T, class K>
+static int ipm_launch_lds(K kern, const std::string& family, int G, size_t bytes,
+                          ipm::Args<T>& a, hipStream_t st) {
+  if (bytes > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void*)kern,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return hip_fail(e, ("hipFuncSetAttribute(" + family + ")").c_str());
+  }
+  hipLaunchKernelGGL(kern, dim3(ipm_grid((a.batch + G - 1) / G, a.list)), dim3(64), bytes, st, a);
+  MPCQP_CHECK_LAUNCH((family + "_kernel").c_str());
+  return MPCQP_OK;
+}
+
 template <typename T>
 static int ipm_quad_launch(ipm::Args<T>& a, hipStream_t st) {
   const int F = ipm::Layout<4, 2>::F;
@@ -162,16 +172,7 @@ static int ipm_quad_launch(ipm::Args<T>& a, hipStream_t st) {
   const size_t bytes = (size_t)G * per;
   const char* wenv = getenv("MPCQP_IPM_WAVE");  // A/B: 0 = the quad kernel at G = 1
   const bool wave = G == 1 && !(wenv && atoi(wenv) == 0);
-  auto launch = [&](auto kern) -> int {
-    if (bytes > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-      if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(ipm_quad)");
-    }
-    hipLaunchKernelGGL(kern, dim3(ipm_grid((a.batch + G - 1) / G, a.list)), dim3(64), bytes, st, a);
-    MPCQP_CHECK_LAUNCH("ipm_quad_kernel");
-    return MPCQP_OK;
-  };
+  auto launch = [&](auto kern) { return ipm_launch_lds(kern, "ipm_quad", G, bytes, a, st); };
   if (G == 4) return launch(ipm_quad_kernel<T, 4>);
   if (G == 2) return launch(ipm_quad_kernel<T, 2>);
   if (wave) return launch(ipm_wave_kernel<T>);
@@ -193,25 +194,15 @@ static int ipm_launch_t(ipm::Args<T>& a, hipStream_t st) {
   }
   const int F = ipm::Layout<NX, NU>::F;
   const int G = ipm_lds_group(a.batch, F, a.N);
-  const dim3 blk(64);
   if (G > 0) {
     const size_t bytes = (size_t)G * a.N * F * sizeof(double);
-    auto launch = [&](auto kern) -> int {
-      if (bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(ipm_lds)");
-      }
-      hipLaunchKernelGGL(kern, dim3(ipm_grid((a.batch + G - 1) / G, a.list)), blk, bytes, st, a);
-      MPCQP_CHECK_LAUNCH("ipm_lds_kernel");
-      return MPCQP_OK;
-    };
+    auto launch = [&](auto kern) { return ipm_launch_lds(kern, "ipm_lds", G, bytes, a, st); };
     if (G == 4) return launch(ipm_lds_kernel<T, NX, NU, 4>);
     if (G == 2) return launch(ipm_lds_kernel<T, NX, NU, 2>);
     return launch(ipm_lds_kernel<T, NX, NU, 1>);
   }
-  hipLaunchKernelGGL((ipm_kernel<T, NX, NU>), dim3(ipm_grid((a.batch + 63) / 64, a.list)), blk, 0,
-                     st, a);
+  hipLaunchKernelGGL((ipm_kernel<T, NX, NU>), dim3(ipm_grid((a.batch + 63) / 64, a.list)), dim3(64),
+                     0, st, a);
   MPCQP_CHECK_LAUNCH("ipm_kernel");
   return MPCQP_OK;
 }
@@ -276,6 +267,8 @@ int mpc_ipm_impl(int dtype, int batch, int nx, int nu, int N, int flags, const v
   fill(a, 0.0f);
   return ipm_launch(a, st);
 }
+
+#undef MPCQP_INLINE_LAMBDA
 
 }  // namespace mpcqp
 

@@ -28,6 +28,12 @@
 //   4. forward: corrector direction, step length.
 // Once mu is small the active set is guessed and polished to the exact
 // vertex (method of multipliers on the same Riccati structure).
+// The formulas of one bounded component in each pass and in the polish, and
+// the decisions between the passes (non-finite, inertia correction, polish,
+// convergence, iteration limit), are in ipm_step.hpp, shared with the quad
+// and wave solvers (ipm_quad.hpp, ipm_wave.hpp); this file holds the stage
+// loops, the Riccati step and the layout.  It also builds for the host
+// (tools/ipm_host.cpp, tests/test_ipm_host.py).
 // Stage k owns u_k, x_{k+1}, pi_{k+1} (the costate of x_{k+1} = ...), the
 // bound duals of u_k and x_{k+1}, and the factor data; everything lives in a
 // stage-major, field-major workspace (global: instance-minor, one fp64 per
@@ -50,7 +56,7 @@
 #error "define MPCQP_HD before including ipm_lane.hpp"
 #endif
 
-#define MPCQP_IL MPCQP_HD inline __attribute__((always_inline))
+#include "ipm_step.hpp"
 
 namespace mpcqp {
 namespace ipm {
@@ -123,9 +129,6 @@ struct Args {
   int list_begin;  // list mode: entries list_begin .. *list_count
 };
 
-constexpr double kInf = __builtin_huge_val();
-
-MPCQP_IL bool fin(double v) { return __builtin_isfinite(v); }
 MPCQP_IL constexpr int pk(int i, int j) {
   return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i;
 }
@@ -452,12 +455,9 @@ MPCQP_IL bool polish(const Args<T>& a, int b, const W& at, const double (&x0)[NX
     ws_bounds<NX, NU>(at, k, lo, hi);
     for (int j = 0; j < NB; ++j) {
       const double vj = j < NU ? at(k, L::U + j) : at(k, L::X + j - NU);
-      const double l = at(k, L::LL + j), u = at(k, L::LU + j);
-      const double rl = fin(lo[j]) ? l / (vj - lo[j]) : 0.0;
-      const double ru = fin(hi[j]) ? u / (hi[j] - vj) : 0.0;
-      const double act = (ru > 1.0 && ru >= rl) ? 1.0 : ((rl > 1.0) ? -1.0 : 0.0);
+      double act, y;
+      polish_guess(vj, lo[j], hi[j], at(k, L::LL + j), at(k, L::LU + j), act, y);
       at(k, L::GA + j) = act;
-      const double y = act > 0.0 ? u : (act < 0.0 ? -l : 0.0);
       if (j < NU) { at(k, L::DU + j) = vj; at(k, L::DUA + j) = y; }
       else { at(k, L::DX + j - NU) = vj; at(k, L::DXA + j - NU) = y; }
     }
@@ -474,7 +474,7 @@ MPCQP_IL bool polish(const Args<T>& a, int b, const W& at, const double (&x0)[NX
   constexpr int kSteps = 4, kRounds = 4;
   const double kRho[kSteps] = {1e8, 1e6, 1e4, 1e4};
   for (int round = 0; round < kRounds; ++round) {
-    bool good = true, changed = false;
+    bool good = true, changed = false, pass = true;  // (pass: no early exit here)
     for (int step = 0; step < kSteps; ++step) {
       const double rho = kRho[step];
       double Ph[L::SX], ph[NX], gx1[NX];
@@ -497,10 +497,11 @@ MPCQP_IL bool polish(const Args<T>& a, int b, const W& at, const double (&x0)[NX
         double g[NB], sig[NB];
         stage_grad<NX, NU>(at, k, Bm, v, pi, xk, gx1, g);
         for (int j = 0; j < NB; ++j) {
-          const double act = at(k, L::GA + j);
           const double y = j < NU ? at(k, L::DUA + j) : at(k, L::DXA + j - NU);
-          sig[j] = act != 0.0 ? rho : 0.0;
-          if (act != 0.0) g[j] += y + rho * (v[j] - (act > 0.0 ? hi[j] : lo[j]));
+          double pen;
+          const bool on = polish_penalty(at(k, L::GA + j), y, rho, v[j], lo[j], hi[j], pen);
+          sig[j] = on ? rho : 0.0;
+          if (on) g[j] += pen;
         }
         double P[L::SX], p[NX], K[NU][NX], kk[NU], Gi[L::SU];
         good = riccati_stage<NX, NU>(at, k, Am, Bm, e, g, sig, Ph, ph, P, p, K, kk, Gi, 0.0) &&
@@ -522,28 +523,9 @@ MPCQP_IL bool polish(const Args<T>& a, int b, const W& at, const double (&x0)[NX
           double& vr = j < NU ? at(k, L::DU + j) : at(k, L::DX + j - NU);
           const double vj = vr + (j < NU ? du[j] : dxn[j - NU]);
           vr = vj;
-          const double act = at(k, L::GA + j);
-          if (act != 0.0) {
-            double& yr = j < NU ? at(k, L::DUA + j) : at(k, L::DXA + j - NU);
-            const double bnd = act > 0.0 ? hi[j] : lo[j];
-            const double y = yr + rho * (vj - bnd);
-            yr = y;
-            if (last) {
-              good = good && fabs(vj - bnd) <= 1e-9 * (1.0 + fabs(bnd));
-              if (act > 0.0 ? y < -1e-9 * (1.0 + fabs(y)) : y > 1e-9 * (1.0 + fabs(y))) {
-                at(k, L::GA + j) = 0.0;  // wrong sign: release
-                yr = 0.0;
-                changed = true;
-              }
-            }
-          } else if (last) {
-            const double jl = (lo[j] - vj) / (1.0 + fabs(lo[j]));
-            const double jh = (vj - hi[j]) / (1.0 + fabs(hi[j]));
-            if (jl > 1e-9 || jh > 1e-9) {  // violated: fix at the violated side
-              at(k, L::GA + j) = jl > jh ? -1.0 : 1.0;
-              changed = true;
-            }
-          }
+          double& yr = j < NU ? at(k, L::DUA + j) : at(k, L::DXA + j - NU);
+          polish_update(vj, lo[j], hi[j], rho, last, false, at(k, L::GA + j), yr, good, changed,
+                        pass);
         }
       });
     }
@@ -662,20 +644,8 @@ MPCQP_IL void solve_lane(const Args<T>& a, int b, double* W) {
   }
 
   // every exit writes the outputs and returns from inside the loop
-  double alpha = 0.0, sigmu = 0.0;  // step and sigma*mu of the last corrector
-  double mu_pol = a.mu_polish;      // next polish attempt below this mu
-  // inertia correction (only a non-convex H2 needs it): on a non-positive
-  // pivot pass 1 runs again with a growing dreg; each iteration starts a third
-  // below the last one that worked (0 once it falls below 1e-12).  It changes
-  // the Newton direction, not the residuals, so the iterate still converges
-  // to a KKT point of the QP.  Strict mode (an SQP's QP, whose caller can
-  // damp the Hessian instead) gives up after a.strict corrections: a QP that
-  // is non-convex only away from its active face needs a few while the
-  // barrier terms of the active bounds grow; one that keeps needing them is
-  // handed back to the caller.
-  double dreg = 0.0, dlast = 0.0;
-  int ncorr = 0;
-  const int max_iter = a.max_iter;
+  Control c;
+  c.mu_pol = a.mu_polish;
   for (int it = 0;; ++it) {
     // ======================================== pass 1: backward factorisation
     double Ph[L::SX], ph[NX], gx1[NX];
@@ -691,28 +661,16 @@ MPCQP_IL void solve_lane(const Args<T>& a, int b, double* W) {
       // x_k: the previous stage's state (its own pass applies the same step)
       for (int i = 0; i < NX; ++i) {
         xk[i] = k == 0 ? x0[i] : at(k - 1, L::X + i);
-        if (alpha > 0.0 && k > 0) xk[i] += alpha * at(k - 1, L::DX + i);
+        if (c.alpha > 0.0 && k > 0) xk[i] += c.alpha * at(k - 1, L::DX + i);
       }
       ws_bounds<NX, NU>(at, k, lo, hi);
-      if (alpha > 0.0) {  // apply the corrector step of the previous iteration
+      if (c.alpha > 0.0) {  // apply the corrector step of the previous iteration
         for (int j = 0; j < NB; ++j) {
           const double dv = j < NU ? at(k, L::DU + j) : at(k, L::DX + j - NU);
           const double dva = j < NU ? at(k, L::DUA + j) : at(k, L::DXA + j - NU);
-          if (fin(lo[j])) {
-            const double sl = v[j] - lo[j];
-            const double dla = -ll[j] * (1.0 + dva / sl);
-            const double rc = sigmu - sl * ll[j] - dva * dla;
-            ll[j] += alpha * ((rc - ll[j] * dv) / sl);
-          }
-          if (fin(hi[j])) {
-            const double su = hi[j] - v[j];
-            const double dua = -lu[j] * (1.0 - dva / su);
-            const double rc = sigmu - su * lu[j] + dva * dua;
-            lu[j] += alpha * ((rc + lu[j] * dv) / su);
-          }
-          v[j] += alpha * dv;
+          apply_step(v[j], ll[j], lu[j], lo[j], hi[j], dv, dva, c.alpha, c.sigmu);
         }
-        for (int i = 0; i < NX; ++i) pi[i] += alpha * at(k, L::DPI + i);
+        for (int i = 0; i < NX; ++i) pi[i] += c.alpha * at(k, L::DPI + i);
         for (int j = 0; j < NU; ++j) at(k, L::U + j) = v[j];
         for (int i = 0; i < NX; ++i) { at(k, L::X + i) = v[NU + i]; at(k, L::PI + i) = pi[i]; }
         for (int j = 0; j < NB; ++j) { at(k, L::LL + j) = ll[j]; at(k, L::LU + j) = lu[j]; }
@@ -732,27 +690,12 @@ MPCQP_IL void solve_lane(const Args<T>& a, int b, double* W) {
       stage_grad<NX, NU>(at, k, Bm, v, pi, xk, gx1, g);
       // stationarity residual, complementarity, Sigma
       double sig[NB];
-      for (int j = 0; j < NB; ++j) {
-        double sj = 0.0;
-        double r = g[j];
-        if (fin(lo[j])) {
-          const double sl = v[j] - lo[j];
-          sj += ll[j] / sl;
-          musum += sl * ll[j];
-          r -= ll[j];
-        }
-        if (fin(hi[j])) {
-          const double su = hi[j] - v[j];
-          sj += lu[j] / su;
-          musum += su * lu[j];
-          r += lu[j];
-        }
-        sig[j] = sj;
-        rstat = fmax(rstat, fabs(r));
-      }
+      for (int j = 0; j < NB; ++j)
+        sig[j] = residual_sigma(v[j], ll[j], lu[j], lo[j], hi[j], g[j], rstat, musum);
       for (int j = 0; j < NB; ++j) at(k, L::GA + j) = g[j];
       double P[L::SX], p[NX], K[NU][NX], kk[NU], Gi[L::SU];
-      const bool ok = riccati_stage<NX, NU>(at, k, Am, Bm, e, g, sig, Ph, ph, P, p, K, kk, Gi, dreg);
+      const bool ok = riccati_stage<NX, NU>(at, k, Am, Bm, e, g, sig, Ph, ph, P, p, K, kk, Gi,
+                                            c.dreg);
       pd = pd && ok;
       store_factor<NX, NU>(at, k, P, p, K, kk, Gi, e);
       next_gx1<NX, NU>(at, k, Am, pi, v, gx1);
@@ -760,46 +703,21 @@ MPCQP_IL void solve_lane(const Args<T>& a, int b, double* W) {
     const double mu = mcount ? musum / mcount : 0.0;
 #ifdef MPCQP_IPM_TRACE  // host build of tools/ipm_host.cpp only
     printf("it %3d mu %.3e rstat %.3e rdyn %.3e pd %d dreg %.2e alpha %.3e\n", it, mu, rstat,
-           rdyn, (int)pd, dreg, alpha);
+           rdyn, (int)pd, c.dreg, c.alpha);
 #endif
-    if (!fin(rstat) || !fin(rdyn) || !fin(mu)) {
-      emit<T, NX, NU>(a, b, at, false, MPCQP_STATUS_NONFINITE, it);
-      return;
-    }
-    if (!pd) {
-      dreg = dreg > 0.0 ? 8.0 * dreg : (dlast > 0.0 ? dlast : 1e-4);
-      if ((a.strict > 0 && ++ncorr > a.strict) || dreg > 1e12 || it >= max_iter) {
-        emit<T, NX, NU>(a, b, at, false, MPCQP_STATUS_NOT_CONVEX, it);
-        return;
-      }
-      alpha = 0.0;  // the pending step is applied already
-      continue;
-    }
-    if (dreg > 0.0) {  // next iteration starts a third lower
-      dlast = dreg;
-      dreg = dreg / 3.0 > 1e-12 ? dreg / 3.0 : 0.0;
-    }
-
-    const bool conv = rstat <= a.tol && rdyn <= a.tol && mu <= a.tol_mu;
-    if (mcount && mu_pol > 0.0 && mu <= mu_pol && rstat <= a.tol_polish && rdyn <= a.tol_polish) {
+    Next next = after_factor(c, a, it, pd, rstat, rdyn, mu, mcount != 0);
+    if (next == kPolish) {
       if (polish<T, NX, NU>(a, b, at, x0)) {
         emit<T, NX, NU>(a, b, at, true, MPCQP_STATUS_OPTIMAL, it);
         return;
       }
-      // wrong active-set guess: keep iterating, try again at a smaller mu;
-      // the polish overwrote the factorisation, so pass 1 runs again
-      mu_pol *= 1e-2;
-      alpha = 0.0;
-      if (conv || it >= max_iter) {
-        emit<T, NX, NU>(a, b, at, false, conv ? MPCQP_STATUS_OPTIMAL : MPCQP_STATUS_MAXITER, it);
-        return;
-      }
-      continue;
+      next = after_failed_polish(c, a, it);
     }
-    if (conv || it >= max_iter) {
-      emit<T, NX, NU>(a, b, at, false, conv ? MPCQP_STATUS_OPTIMAL : MPCQP_STATUS_MAXITER, it);
+    if (next == kStop) {
+      emit<T, NX, NU>(a, b, at, false, c.code, it);
       return;
     }
+    if (next == kAgain) continue;
 
     // ========================================== pass 2: forward predictor
     double amax = 1.0, c0 = 0.0, c1 = 0.0, c2 = 0.0;
@@ -811,33 +729,11 @@ MPCQP_IL void solve_lane(const Args<T>& a, int b, double* W) {
       for (int j = 0; j < NB; ++j) {
         const double vj = j < NU ? at(k, L::U + j) : at(k, L::X + j - NU);
         const double dv = j < NU ? du[j] : dxn[j - NU];
-        if (fin(lo[j])) {
-          const double sl = vj - lo[j], l = at(k, L::LL + j);
-          const double dl = -l * (1.0 + dv / sl);
-          if (dv < 0.0) amax = fmin(amax, -sl / dv);
-          if (dl < 0.0) amax = fmin(amax, -l / dl);
-          c0 += sl * l;
-          c1 += sl * dl + l * dv;
-          c2 += dv * dl;
-        }
-        if (fin(hi[j])) {
-          const double su = hi[j] - vj, l = at(k, L::LU + j);
-          const double dl = -l * (1.0 - dv / su);
-          if (dv > 0.0) amax = fmin(amax, su / dv);
-          if (dl < 0.0) amax = fmin(amax, -l / dl);
-          c0 += su * l;
-          c1 += su * dl - l * dv;
-          c2 -= dv * dl;
-        }
+        predictor_terms(vj, dv, lo[j], hi[j], at(k, L::LL + j), at(k, L::LU + j), amax, c0, c1,
+                        c2);
       }
     });
-    if (mcount) {
-      const double mua = (c0 + amax * (c1 + amax * c2)) / mcount;
-      const double r = fmax(0.0, fmin(1.0, mua / mu));
-      sigmu = r * r * r * mu;
-    } else {
-      sigmu = 0.0;
-    }
+    c.sigmu = centering(mcount, c0, c1, c2, amax, mu);
 
     // ================================ pass 3: backward corrector right side
     {
@@ -849,16 +745,8 @@ MPCQP_IL void solve_lane(const Args<T>& a, int b, double* W) {
         for (int j = 0; j < NB; ++j) {
           const double vj = j < NU ? at(k, L::U + j) : at(k, L::X + j - NU);
           const double dva = j < NU ? at(k, L::DUA + j) : at(k, L::DXA + j - NU);
-          double s = at(k, L::GA + j);
-          if (fin(lo[j])) {
-            const double sl = vj - lo[j], l = at(k, L::LL + j);
-            s += (-sigmu - dva * l * (1.0 + dva / sl)) / sl;
-          }
-          if (fin(hi[j])) {
-            const double su = hi[j] - vj, l = at(k, L::LU + j);
-            s += (sigmu - dva * l * (1.0 - dva / su)) / su;
-          }
-          g[j] = s;
+          g[j] = corrector_rhs(vj, dva, lo[j], hi[j], at(k, L::LL + j), at(k, L::LU + j),
+                               at(k, L::GA + j), c.sigmu);
         }
         double p[NX], Pe[NX];
         for (int i = 0; i < NX; ++i) p[i] = g[NU + i] + phc[i];
@@ -906,26 +794,11 @@ MPCQP_IL void solve_lane(const Args<T>& a, int b, double* W) {
         const double vj = j < NU ? at(k, L::U + j) : at(k, L::X + j - NU);
         const double dv = j < NU ? du[j] : dxn[j - NU];
         const double dva = j < NU ? at(k, L::DUA + j) : at(k, L::DXA + j - NU);
-        if (fin(lo[j])) {
-          const double sl = vj - lo[j], l = at(k, L::LL + j);
-          const double dla = -l * (1.0 + dva / sl);
-          const double dl = (sigmu - sl * l - dva * dla - l * dv) / sl;
-          if (dv < 0.0) amax = fmin(amax, -sl / dv);
-          if (dl < 0.0) amax = fmin(amax, -l / dl);
-        }
-        if (fin(hi[j])) {
-          const double su = hi[j] - vj, l = at(k, L::LU + j);
-          const double dua = -l * (1.0 - dva / su);
-          const double dl = (sigmu - su * l + dva * dua + l * dv) / su;
-          if (dv > 0.0) amax = fmin(amax, su / dv);
-          if (dl < 0.0) amax = fmin(amax, -l / dl);
-        }
+        corrector_bound(vj, dv, dva, lo[j], hi[j], at(k, L::LL + j), at(k, L::LU + j), c.sigmu,
+                        amax);
       }
     });
-    // fraction to the boundary.  Fixed, not tightened towards 1 as mu -> 0:
-    // the slacks are differences v - lo, and a slack driven below the rounding
-    // of v would turn Sigma = lam / s into inf
-    alpha = fmin(1.0, 0.995 * amax);
+    c.alpha = step_length(amax);
   }
 }
 

@@ -9,11 +9,18 @@
 // per instance, and a wave holds 16 instances instead of 1-4.
 //
 // Same algorithm, workspace layout (Layout<4, 2>), arguments and outputs as
-// ipm_lane.hpp (solve_lane); the workspace is a slice of LDS (LD instances
-// interleaved), so a value one lane stores is read by the others in program
-// order.  Every decision (step length, convergence, polish, inertia) is made
-// on quad-reduced values, so the four lanes of an instance take the same
-// branches.  Device only (DPP).
+// ipm_lane.hpp (solve_lane), and the same code for the algebra of a bounded
+// component and for the decisions between the passes (ipm_step.hpp); the
+// workspace is a slice of LDS (LD instances interleaved), so a value one lane
+// stores is read by the others in program order.  Every decision (step
+// length, convergence, polish, inertia) is made on quad-reduced values, so
+// the four lanes of an instance take the same branches.  Device only (DPP).
+//
+// The work of one stage in each pass and in the polish is one function each
+// (start_stage_q, pass1..4_stage_q, polish_init_q / _grad_q / _check_q):
+// solve_quad and polish_q call them along the horizon, solve_wave and polish_w
+// (ipm_wave.hpp) one quad per stage.  The chain of pass 3 is rhs_step_q for
+// ipm_wave.hpp's quad form; solve_quad keeps it inline.
 #pragma once
 
 #include "sym2d.hpp"
@@ -329,148 +336,326 @@ MPCQP_QD void forward_q(const W& at, int N, int i, Body&& body) {
   }
 }
 
+// ------------------------------------------------- per-stage bodies
+// The work of one stage in each pass and in the polish, lane i of the stage's
+// quad (state comp i; lanes 0, 1 also input comp i), on the component algebra
+// of ipm_step.hpp.  solve_quad / polish_q call them from their serial loops
+// over the horizon and pass the results on in registers; solve_wave / polish_w
+// (ipm_wave.hpp) call them one quad per stage and put the results into
+// workspace fields for the serial chains.
+
+// What the per-stage part of pass 1 (pass1_stage_q) and of a polish step
+// (polish_grad_q) hands to the factorisation of the stage and to the stage
+// before it.
+struct StageOutQ {
+  StageQ S;
+  double e;              // dynamics residual, row i
+  double gx, gu[2];      // gradients: g_x[i]; both inputs, replicated
+  double sx, sui;        // Sigma (polish: penalty) of state comp i, of input comp i (0: i >= 2)
+  double pia[4], ua[2];  // pi_{k+1}, u_k, replicated (next_gx1_q)
+};
+
+// Stage data of stage k (stage_in_q) -> the start point: inputs inside their
+// box, states rolled out (xi: x_k row i in, x_{k+1} out) and pushed inside
+// theirs, pi = 0, duals = 1; mc += the finite bounds this lane owns.
+template <typename T, class W>
+MPCQP_QD void start_stage_q(const Args<T>& a, int b, const W& at, int i, int k, double& xi,
+                            double& mc) {
+  const bool ou = i < NU;
+  const double ci = at.r(k, L::DC);
+  double ui = 0.0;
+  if (ou) {
+    const double u0 =
+        (a.U0 && i < a.nu) ? (double)a.U0[(int64_t)b * a.sU0 + (int64_t)k * a.nu + i] : 0.0;
+    ui = interior(u0, at.r(k, L::LO), at.r(k, L::HI));
+    at.r(k, L::U) = ui;
+  }
+  double xa[4], ua[2];
+  bcast4(xi, xa);
+  ua[0] = qb<0>(ui);
+  ua[1] = qb<1>(ui);
+  double s = ci;
+#pragma unroll
+  for (int j = 0; j < NX; ++j) s = fma(at.ra(k, L::DA + j), xa[j], s);
+#pragma unroll
+  for (int r = 0; r < NU; ++r) s = fma(at.rb(k, L::DB + r), ua[r], s);
+  const double lox = at.r(k, L::LO + NU), hix = at.r(k, L::HI + NU);
+  xi = interior(s, lox, hix);
+  at.r(k, L::X) = xi;
+  at.r(k, L::PI) = 0.0;
+  at.r(k, L::LL + NU) = fin(lox) ? 1.0 : 0.0;
+  at.r(k, L::LU + NU) = fin(hix) ? 1.0 : 0.0;
+  mc += (fin(lox) ? 1.0 : 0.0) + (fin(hix) ? 1.0 : 0.0);
+  if (ou) {
+    const double lou = at.r(k, L::LO), hiu = at.r(k, L::HI);
+    at.r(k, L::LL) = fin(lou) ? 1.0 : 0.0;
+    at.r(k, L::LU) = fin(hiu) ? 1.0 : 0.0;
+    mc += (fin(lou) ? 1.0 : 0.0) + (fin(hiu) ? 1.0 : 0.0);
+  }
+}
+
+// Pass 1 of stage k: apply the previous corrector step (c.alpha > 0) to the
+// stage's iterate, then the dynamics residual (-> rdyn), the gradients (also
+// -> GA), the stationarity residual (-> rstat), complementarity (-> musum) and
+// Sigma.  xki = x_k row i after the step, gx1 = the later stage's
+// A'pi + H2xu u row i after the step.
+template <class W>
+MPCQP_QD void pass1_stage_q(const W& at, int i, int k, double xki, double gx1,
+                            const ipm::Control& c, double& rstat, double& rdyn, double& musum,
+                            StageOutQ& o) {
+  const bool ou = i < NU;
+  double xi = at.r(k, L::X), pii = at.r(k, L::PI);
+  double llx = at.r(k, L::LL + NU), lux = at.r(k, L::LU + NU);
+  double ui = 0.0, llu = 0.0, luu = 0.0;
+  if (ou) { ui = at.r(k, L::U); llu = at.r(k, L::LL); luu = at.r(k, L::LU); }
+  const double lox = at.r(k, L::LO + NU), hix = at.r(k, L::HI + NU);
+  const double lou = ou ? at.r(k, L::LO) : -kInf, hiu = ou ? at.r(k, L::HI) : kInf;
+  if (c.alpha > 0.0) {
+    ipm::apply_step(xi, llx, lux, lox, hix, at.r(k, L::DX), at.r(k, L::DXA), c.alpha, c.sigmu);
+    if (ou)
+      ipm::apply_step(ui, llu, luu, lou, hiu, at.r(k, L::DU), at.r(k, L::DUA), c.alpha, c.sigmu);
+    pii += c.alpha * at.r(k, L::DPI);
+    at.r(k, L::X) = xi;
+    at.r(k, L::PI) = pii;
+    at.r(k, L::LL + NU) = llx;
+    at.r(k, L::LU + NU) = lux;
+    if (ou) { at.r(k, L::U) = ui; at.r(k, L::LL) = llu; at.r(k, L::LU) = luu; }
+  }
+  double xa[4], x1a[4];
+  bcast4(xki, xa);
+  bcast4(xi, x1a);
+  bcast4(pii, o.pia);
+  o.ua[0] = qb<0>(ui);
+  o.ua[1] = qb<1>(ui);
+  o.S.load(at, k);
+  o.e = resid_q(at, o.S, k, i, xa, o.ua, xi);
+  rdyn = fmax(rdyn, fabs(o.e));
+  grad_q(at, o.S, k, i, xa, x1a, o.pia, o.ua, pii, gx1, o.gx, o.gu);
+  o.sx = ipm::residual_sigma(xi, llx, lux, lox, hix, o.gx, rstat, musum);
+  at.r(k, L::GA + NU) = o.gx;
+  o.sui = 0.0;
+  if (ou) {
+    const double gui = sel2(o.gu, i);
+    o.sui = ipm::residual_sigma(ui, llu, luu, lou, hiu, gui, rstat, musum);
+    at.r(k, L::GA) = gui;
+  }
+}
+
+// Pass 2 of stage k: the predictor directions dxn (state comp i) and dun
+// (input comp i, owners): step to the boundary and affine complementarity.
+template <class W>
+MPCQP_QD void pass2_stage_q(const W& at, int i, int k, double dxn, double dun, double& amax,
+                            double& c0, double& c1, double& c2) {
+  ipm::predictor_terms(at.r(k, L::X), dxn, at.r(k, L::LO + NU), at.r(k, L::HI + NU),
+                       at.r(k, L::LL + NU), at.r(k, L::LU + NU), amax, c0, c1, c2);
+  if (i < NU)
+    ipm::predictor_terms(at.r(k, L::U), dun, at.r(k, L::LO), at.r(k, L::HI), at.r(k, L::LL),
+                         at.r(k, L::LU), amax, c0, c1, c2);
+}
+
+// Pass 3 of stage k: the corrector right-hand sides gx (state comp i) and
+// gum (input comp i; 0 on lanes 2, 3) from the gradients in GA and the
+// predictor in DXA / DUA.
+template <class W>
+MPCQP_QD void pass3_stage_q(const W& at, int i, int k, double sigmu, double& gx, double& gum) {
+  gx = ipm::corrector_rhs(at.r(k, L::X), at.r(k, L::DXA), at.r(k, L::LO + NU),
+                          at.r(k, L::HI + NU), at.r(k, L::LL + NU), at.r(k, L::LU + NU),
+                          at.r(k, L::GA + NU), sigmu);
+  gum = i < NU ? ipm::corrector_rhs(at.r(k, L::U), at.r(k, L::DUA), at.r(k, L::LO),
+                                    at.r(k, L::HI), at.r(k, L::LL), at.r(k, L::LU),
+                                    at.r(k, L::GA), sigmu)
+               : 0.0;
+}
+
+// One step of the backward chain of a right-hand side on the stored
+// factorisation (pass 3; a polish step that keeps its factors): in gx (row i),
+// gu (replicated) and phc, the cost-to-go's linear term from the later stages;
+// writes k -> KV, p -> PV and leaves phc for the stage before.
+template <class W>
+MPCQP_QD void rhs_step_q(const W& at, int i, int k, double gx, const double (&gu)[2],
+                         double& phc) {
+  const double p = gx + phc;
+  double Pe = p;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) Pe = fma(at.p(k, L::PP, j), at(k, L::E + j), Pe);
+  double Pea[4];
+  bcast4(Pe, Pea);
+  double h[2];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    double s = gu[r];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s = fma(at(k, L::DB + q * NU + r), Pea[q], s);
+    h[r] = s;
+  }
+  const double Gi[3] = {at(k, L::GI + 0), at(k, L::GI + 1), at(k, L::GI + 2)};
+  double kk[2];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) kk[r] = -(Gi[pk(r, 0)] * h[0] + Gi[pk(r, 1)] * h[1]);
+  if (i < NU) at.r(k, L::KV) = sel2(kk, i);
+  // ph = A'Pe + K'h
+  double s = 0.0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) s = fma(at.r(k, L::DA + q * NX), Pea[q], s);
+#pragma unroll
+  for (int r = 0; r < 2; ++r) s = fma(at.r(k, L::KM + r * NX), h[r], s);
+  phc = s;
+  at.r(k, L::PV) = p;
+}
+
+// Pass 4 of stage k: the costate direction dpi = P dx+ + p -> DPI (dxa: the
+// state direction of x_{k+1}, replicated) and the step to the boundary of the
+// corrector directions dxn, dun.
+template <class W>
+MPCQP_QD void pass4_stage_q(const W& at, int i, int k, double dxn, double dun,
+                            const double (&dxa)[4], double sigmu, double& amax) {
+  double s = at.r(k, L::PV);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) s = fma(at.p(k, L::PP, j), dxa[j], s);
+  at.r(k, L::DPI) = s;
+  ipm::corrector_bound(at.r(k, L::X), dxn, at.r(k, L::DXA), at.r(k, L::LO + NU),
+                       at.r(k, L::HI + NU), at.r(k, L::LL + NU), at.r(k, L::LU + NU), sigmu,
+                       amax);
+  if (i < NU)
+    ipm::corrector_bound(at.r(k, L::U), dun, at.r(k, L::DUA), at.r(k, L::LO), at.r(k, L::HI),
+                         at.r(k, L::LL), at.r(k, L::LU), sigmu, amax);
+}
+
 // ------------------------------------------------------------- polish
 // The polish of ipm_lane.hpp (see there), lane i owning state comp i and
 // (i < 2) input comp i.
 // warm: the active set is the one GA already holds (the previous QP's polish,
 // solve_quad's warm start) and the multipliers start at 0; otherwise it is
 // guessed from the interior-point iterate (lambda > slack) with its duals.
+
+// Initialisation of stage k: the iterate -> DX / DU / DPI, the active flags
+// -> GA and the multipliers -> DXA / DUA.
+template <class W>
+MPCQP_QD void polish_init_q(const W& at, int i, int k, bool warm) {
+  // state comp i, then input comp i
+#pragma unroll
+  for (int part = 0; part < 2; ++part) {
+    if (part == 1 && i >= NU) continue;
+    const int j = part == 0 ? NU + i : i;
+    const double vj = part == 0 ? at.r(k, L::X) : at.r(k, L::U);
+    double y = 0.0;
+    if (!warm) {
+      double act;
+      ipm::polish_guess(vj, at(k, L::LO + j), at(k, L::HI + j), at(k, L::LL + j),
+                        at(k, L::LU + j), act, y);
+      at(k, L::GA + j) = act;
+    }
+    if (part == 1) { at.r(k, L::DU) = vj; at.r(k, L::DUA) = y; }
+    else { at.r(k, L::DX) = vj; at.r(k, L::DXA) = y; }
+  }
+  at.r(k, L::DPI) = at.r(k, L::PI);
+}
+
+// One step's residual and gradients of stage k with the penalty of the active
+// components (curvature in o.sx / o.sui).  xki = x_k row i, gx1 as pass1_stage_q.
+template <class W>
+MPCQP_QD void polish_grad_q(const W& at, int i, int k, double rho, double xki, double gx1,
+                            StageOutQ& o) {
+  const bool ou = i < NU;
+  const double xi = at.r(k, L::DX), pii = at.r(k, L::DPI);
+  const double ui = ou ? at.r(k, L::DU) : 0.0;
+  double xa[4], x1a[4];
+  bcast4(xki, xa);
+  bcast4(xi, x1a);
+  bcast4(pii, o.pia);
+  o.ua[0] = qb<0>(ui);
+  o.ua[1] = qb<1>(ui);
+  o.S.load(at, k);
+  o.e = resid_q(at, o.S, k, i, xa, o.ua, xi);
+  grad_q(at, o.S, k, i, xa, x1a, o.pia, o.ua, pii, gx1, o.gx, o.gu);
+  // the penalty of the active components: state comp i, inputs (owners)
+  o.sx = o.sui = 0.0;
+  double pen, gum = 0.0;
+  if (ipm::polish_penalty(at.r(k, L::GA + NU), at.r(k, L::DXA), rho, xi, at.r(k, L::LO + NU),
+                          at.r(k, L::HI + NU), pen)) {
+    o.sx = rho;
+    o.gx += pen;
+  }
+  if (ou && ipm::polish_penalty(at.r(k, L::GA), at.r(k, L::DUA), rho, ui, at.r(k, L::LO),
+                                at.r(k, L::HI), pen)) {
+    o.sui = rho;
+    gum = pen;
+  }
+  o.gu[0] += qb<0>(gum);
+  o.gu[1] += qb<1>(gum);
+}
+
+// After the step of stage k (vx, vu: the new state comp i and input comp i):
+// the costate update (dxa: the state direction of x_{k+1}, replicated), the
+// multipliers and the accept / release / add tests (ipm::polish_update).
+template <class W>
+MPCQP_QD void polish_check_q(const W& at, int i, int k, const double (&dxa)[4], double vx,
+                             double vu, double rho, bool last, bool probe, bool& good,
+                             bool& changed, bool& pass) {
+  double s = at.r(k, L::PV);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) s = fma(at.p(k, L::PP, j), dxa[j], s);
+  at.r(k, L::DPI) += s;
+  ipm::polish_update(vx, at.r(k, L::LO + NU), at.r(k, L::HI + NU), rho, last, probe,
+                     at.r(k, L::GA + NU), at.r(k, L::DXA), good, changed, pass);
+  if (i < NU)
+    ipm::polish_update(vu, at.r(k, L::LO), at.r(k, L::HI), rho, last, probe, at.r(k, L::GA),
+                       at.r(k, L::DUA), good, changed, pass);
+}
+
+// The polish's schedule: steps per round (penalties 1e8, 1e6, 1e4, 1e4) and
+// rounds; kPolishEarly: from this step on a step whose result already passes
+// the last step's test (active components on their bound to 1e-9, multipliers
+// of the right sign, no inactive component violated) ends the polish.
+constexpr int kPolishSteps = 4, kPolishRounds = 4;
+#ifdef MPCQP_POLISH_EARLY
+constexpr int kPolishEarly = MPCQP_POLISH_EARLY;
+#else
+constexpr int kPolishEarly = kPolishSteps;  // (off: every round runs all four steps)
+#endif
+MPCQP_QD double polish_rho(int step) { return step == 0 ? 1e8 : (step == 1 ? 1e6 : 1e4); }
+MPCQP_QD int polish_rounds(bool warm) {
+#ifdef MPCQP_WARM_ROUNDS
+  // a warm polish whose active set needs corrections hands over to the
+  // interior point after this many rounds (timing builds)
+  if (warm) return MPCQP_WARM_ROUNDS;
+#endif
+  return kPolishRounds;
+}
+
 template <typename T, class W>
 MPCQP_QD bool polish_q(const Args<T>& a, const W& at, int i, double x0i, bool warm = false) {
   const int N = a.N;
   const bool ou = i < NU;
-  for (int k = 0; k < N; ++k) {
-    // state comp i, then input comp i
-#pragma unroll
-    for (int part = 0; part < 2; ++part) {
-      if (part == 1 && !ou) continue;
-      const int j = part == 0 ? NU + i : i;
-      const double vj = part == 0 ? at.r(k, L::X) : at.r(k, L::U);
-      double y = 0.0;
-      if (!warm) {
-        const double lo = at(k, L::LO + j), hi = at(k, L::HI + j);
-        const double l = at(k, L::LL + j), u = at(k, L::LU + j);
-        const double rl = fin(lo) ? l / (vj - lo) : 0.0;
-        const double ru = fin(hi) ? u / (hi - vj) : 0.0;
-        const double act = (ru > 1.0 && ru >= rl) ? 1.0 : ((rl > 1.0) ? -1.0 : 0.0);
-        at(k, L::GA + j) = act;
-        y = act > 0.0 ? u : (act < 0.0 ? -l : 0.0);
-      }
-      if (part == 1) { at.r(k, L::DU) = vj; at.r(k, L::DUA) = y; }
-      else { at.r(k, L::DX) = vj; at.r(k, L::DXA) = y; }
-    }
-    at.r(k, L::DPI) = at.r(k, L::PI);
-  }
-  constexpr int kSteps = 4, kRounds = 4;
-#ifdef MPCQP_POLISH_EARLY
-  constexpr int kPolishEarly = MPCQP_POLISH_EARLY;
-#else
-  constexpr int kPolishEarly = kSteps;  // (off: every round runs all four steps)
-#endif
-#ifdef MPCQP_WARM_ROUNDS
-  // a warm polish whose active set needs corrections hands over to the
-  // interior point after this many rounds (timing builds)
-  const int rounds = warm ? MPCQP_WARM_ROUNDS : kRounds;
-#else
-  const int rounds = kRounds;
-#endif
+  for (int k = 0; k < N; ++k) polish_init_q(at, i, k, warm);
+  const int rounds = polish_rounds(warm);
   for (int round = 0; round < rounds; ++round) {
     bool good = true, changed = false;
-    for (int step = 0; step < kSteps; ++step) {
-      const double rho = step == 0 ? 1e8 : (step == 1 ? 1e6 : 1e4);
+    for (int step = 0; step < kPolishSteps; ++step) {
+      const double rho = polish_rho(step);
       double Ph[4] = {0.0, 0.0, 0.0, 0.0}, ph = 0.0, gx1 = 0.0;
       for (int k = N - 1; k >= 0; --k) {
-        const double xi = at.r(k, L::DX), pii = at.r(k, L::DPI);
-        const double ui = ou ? at.r(k, L::DU) : 0.0;
-        const double xki = k == 0 ? x0i : at.r(k - 1, L::DX);
-        double xa[4], x1a[4], pia[4], ua[2];
-        bcast4(xki, xa);
-        bcast4(xi, x1a);
-        bcast4(pii, pia);
-        ua[0] = qb<0>(ui);
-        ua[1] = qb<1>(ui);
-        StageQ S;
-        S.load(at, k);
-        const double e = resid_q(at, S, k, i, xa, ua, xi);
-        double gx, gu[2];
-        grad_q(at, S, k, i, xa, x1a, pia, ua, pii, gx1, gx, gu);
-        // the penalty of the active components: state comp i, inputs (owners)
-        double sx = 0.0, sui = 0.0;
-        {
-          const int j = NU + i;
-          const double act = at(k, L::GA + j);
-          if (act != 0.0) {
-            const double bnd = act > 0.0 ? at(k, L::HI + j) : at(k, L::LO + j);
-            sx = rho;
-            gx += at.r(k, L::DXA) + rho * (xi - bnd);
-          }
-        }
-        double gum = 0.0;
-        if (ou) {
-          const double act = at.r(k, L::GA);
-          if (act != 0.0) {
-            const double bnd = act > 0.0 ? at.r(k, L::HI) : at.r(k, L::LO);
-            sui = rho;
-            gum = at.r(k, L::DUA) + rho * (ui - bnd);
-          }
-        }
-        double su2[2] = {qb<0>(sui), qb<1>(sui)};
-        gu[0] += qb<0>(gum);
-        gu[1] += qb<1>(gum);
+        StageOutQ o;
+        polish_grad_q(at, i, k, rho, k == 0 ? x0i : at.r(k - 1, L::DX), gx1, o);
+        const double su2[2] = {qb<0>(o.sui), qb<1>(o.sui)};
         double P[4], p, K[2][4], kk[2], Gi[3], Kc[2];
-        good = riccati_q(at, S, k, i, Ph, ph, e, gx, gu, sx, su2, 0.0, P, p, K, kk, Gi, Kc) && good;
-        store_factor_q(at, k, i, P, p, Kc, kk, Gi, e);
-        gx1 = next_gx1_q(at, S, k, i, pia, ua);
+        good = riccati_q(at, o.S, k, i, Ph, ph, o.e, o.gx, o.gu, o.sx, su2, 0.0, P, p, K, kk, Gi,
+                         Kc) && good;
+        store_factor_q(at, k, i, P, p, Kc, kk, Gi, o.e);
+        gx1 = next_gx1_q(at, o.S, k, i, o.pia, o.ua);
       }
-      const bool last = step == kSteps - 1;
-      // early exit (MPCQP_POLISH_EARLY builds / kPolishEarly): from step
-      // kPolishEarly on, a step whose result already passes the last step's
-      // test (active components on their bound to 1e-9, multipliers of the
-      // right sign, no inactive component violated) ends the polish
+      const bool last = step == kPolishSteps - 1;
       const bool probe = !last && step >= kPolishEarly;
       bool pass = true;
       forward_q(at, N, i, [&](int k, const double (&du)[2], double dxn, const double (&dxa)[4]) {
-        double s = at.r(k, L::PV);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s = fma(at.p(k, L::PP, j), dxa[j], s);
-        at.r(k, L::DPI) += s;
-#pragma unroll
-        for (int part = 0; part < 2; ++part) {
-          if (part == 1 && !ou) continue;
-          const int j = part == 0 ? NU + i : i;
-          double& vr = part == 0 ? at.r(k, L::DX) : at.r(k, L::DU);
-          const double vj = vr + (part == 0 ? dxn : sel2(du, i));
-          vr = vj;
-          const double lo = at(k, L::LO + j), hi = at(k, L::HI + j);
-          const double act = at(k, L::GA + j);
-          if (act != 0.0) {
-            double& yr = part == 0 ? at.r(k, L::DXA) : at.r(k, L::DUA);
-            const double bnd = act > 0.0 ? hi : lo;
-            const double y = yr + rho * (vj - bnd);
-            yr = y;
-            if (probe)
-              pass = pass && fabs(vj - bnd) <= 1e-9 * (1.0 + fabs(bnd)) &&
-                     !(act > 0.0 ? y < -1e-9 * (1.0 + fabs(y)) : y > 1e-9 * (1.0 + fabs(y)));
-            if (last) {
-              good = good && fabs(vj - bnd) <= 1e-9 * (1.0 + fabs(bnd));
-              if (act > 0.0 ? y < -1e-9 * (1.0 + fabs(y)) : y > 1e-9 * (1.0 + fabs(y))) {
-                at(k, L::GA + j) = 0.0;
-                yr = 0.0;
-                changed = true;
-              }
-            }
-          } else if (last || probe) {
-            const double jl = (lo - vj) / (1.0 + fabs(lo));
-            const double jh = (vj - hi) / (1.0 + fabs(hi));
-            if (jl > 1e-9 || jh > 1e-9) {
-              if (last) {
-                at(k, L::GA + j) = jl > jh ? -1.0 : 1.0;
-                changed = true;
-              }
-              pass = false;
-            }
-          }
+        const double vx = at.r(k, L::DX) + dxn;
+        at.r(k, L::DX) = vx;
+        double vu = 0.0;
+        if (ou) {
+          vu = at.r(k, L::DU) + sel2(du, i);
+          at.r(k, L::DU) = vu;
         }
+        polish_check_q(at, i, k, dxa, vx, vu, rho, last, probe, good, changed, pass);
       });
       if (probe && good && qmin(pass ? 1.0 : 0.0) > 0.5) return true;
     }
@@ -508,8 +693,6 @@ MPCQP_QD void emit_q(const Args<T>& a, int b, const W& at, int i, bool polished,
   if (i == 0) a.status[b] = code | ((it & 0xFFFF) << 8) | (polished ? (1 << 24) : 0);
 }
 
-// One instance on the four lanes of a quad (i = lane & 3), workspace slice W
-// (LD instances interleaved).  Requires nx <= 4, nu <= 2.
 // Stage k's data into the workspace, lane i's rows: the bounds, A, B, c, the
 // x_{k+1} cost with H2xx, the coupling H2xu, R + H2uu and q2 (the first half
 // of solve_quad's start; the one-launch SQP runs it one quad per stage).
@@ -554,11 +737,14 @@ MPCQP_QD void stage_in_q(const Args<T>& a, int b, const W& at, int i, int k) {
   }
 }
 
+// One instance on the four lanes of a quad (i = lane & 3), workspace slice W
+// (LD instances interleaved).  Requires nx <= 4, nu <= 2.
 // warm (the one-launch SQP, sqp_solve.hip): the previous QP of this
 // instance ended polished and its active set is still in W's GA fields; the
 // QP is first polished on that active set from the start point, and the
 // interior point runs only if that is not a certified vertex.  Returns true
 // when the QP ended polished (its active set is then in GA for the next one).
+// staged: the stage data are in W already (stage_in_q).
 // MPCQP_IPM_PASSCLK (timing builds, tools/sqp_latency.py): s_memrealtime
 // ticks accumulated into pclk[0..7]: the four passes, the polish, factorisations
 // that failed the inertia test (solve_wave; solve_quad: + the loop head), the
@@ -577,9 +763,9 @@ MPCQP_QD bool solve_quad(const Args<T>& a, int b, double* W, bool warm = false,
   const int i = (int)(threadIdx.x & 3);
   const WsQ<LD> at(W, i);
   const bool ou = i < NU;
-  const int N = a.N, nx = a.nx, nu = a.nu;
+  const int N = a.N;
   if (a.skip && (a.skip[b] & a.skip_mask)) return false;
-  const double x0i = i < nx ? (double)a.x0[(int64_t)b * a.sX0 + i] : 0.0;
+  const double x0i = i < a.nx ? (double)a.x0[(int64_t)b * a.sX0 + i] : 0.0;
 
   // ---------------------------------------------------------------- start
   double mc = 0.0;  // finite bounds owned by this lane
@@ -587,38 +773,7 @@ MPCQP_QD bool solve_quad(const Args<T>& a, int b, double* W, bool warm = false,
     double xi = x0i;
     for (int k = 0; k < N; ++k) {
       if (!staged) stage_in_q(a, b, at, i, k);
-      const double ci = at.r(k, L::DC);
-      // start point: inputs inside their box, states rolled out and pushed
-      // inside theirs, pi = 0, duals = 1
-      double ui = 0.0;
-      if (ou) {
-        const double u0 =
-            (a.U0 && i < nu) ? (double)a.U0[(int64_t)b * a.sU0 + (int64_t)k * nu + i] : 0.0;
-        ui = interior(u0, at.r(k, L::LO), at.r(k, L::HI));
-        at.r(k, L::U) = ui;
-      }
-      double xa[4], ua[2];
-      bcast4(xi, xa);
-      ua[0] = qb<0>(ui);
-      ua[1] = qb<1>(ui);
-      double s = ci;
-#pragma unroll
-      for (int j = 0; j < NX; ++j) s = fma(at.ra(k, L::DA + j), xa[j], s);
-#pragma unroll
-      for (int r = 0; r < NU; ++r) s = fma(at.rb(k, L::DB + r), ua[r], s);
-      const double lox = at.r(k, L::LO + NU), hix = at.r(k, L::HI + NU);
-      xi = interior(s, lox, hix);
-      at.r(k, L::X) = xi;
-      at.r(k, L::PI) = 0.0;
-      at.r(k, L::LL + NU) = fin(lox) ? 1.0 : 0.0;
-      at.r(k, L::LU + NU) = fin(hix) ? 1.0 : 0.0;
-      mc += (fin(lox) ? 1.0 : 0.0) + (fin(hix) ? 1.0 : 0.0);
-      if (ou) {
-        const double lou = at.r(k, L::LO), hiu = at.r(k, L::HI);
-        at.r(k, L::LL) = fin(lou) ? 1.0 : 0.0;
-        at.r(k, L::LU) = fin(hiu) ? 1.0 : 0.0;
-        mc += (fin(lou) ? 1.0 : 0.0) + (fin(hiu) ? 1.0 : 0.0);
-      }
+      start_stage_q(a, b, at, i, k, xi, mc);
     }
   }
   const double mcount = qsum(mc);
@@ -628,11 +783,8 @@ MPCQP_QD bool solve_quad(const Args<T>& a, int b, double* W, bool warm = false,
     return true;
   }
 
-  double alpha = 0.0, sigmu = 0.0;
-  double mu_pol = a.mu_polish;
-  double dreg = 0.0, dlast = 0.0;
-  int ncorr = 0;
-  const int max_iter = a.max_iter;
+  ipm::Control c;
+  c.mu_pol = a.mu_polish;
   for (int it = 0;; ++it) {
     MPCQP_PCLK(5);
     // ======================================== pass 1: backward factorisation
@@ -640,99 +792,24 @@ MPCQP_QD bool solve_quad(const Args<T>& a, int b, double* W, bool warm = false,
     double rstat = 0.0, rdyn = 0.0, musum = 0.0;
     bool pd = true;
     for (int k = N - 1; k >= 0; --k) {
-      double xi = at.r(k, L::X), pii = at.r(k, L::PI);
-      double llx = at.r(k, L::LL + NU), lux = at.r(k, L::LU + NU);
-      double ui = 0.0, llu = 0.0, luu = 0.0;
-      if (ou) { ui = at.r(k, L::U); llu = at.r(k, L::LL); luu = at.r(k, L::LU); }
-      const double lox = at.r(k, L::LO + NU), hix = at.r(k, L::HI + NU);
-      const double lou = ou ? at.r(k, L::LO) : -kInf, hiu = ou ? at.r(k, L::HI) : kInf;
+      // x_k: the previous stage's state (its own pass applies the same step)
       double xki = k == 0 ? x0i : at.r(k - 1, L::X);
-      if (alpha > 0.0 && k > 0) xki += alpha * at.r(k - 1, L::DX);
-      if (alpha > 0.0) {  // apply the corrector step of the previous iteration
-        auto apply = [&](double& v, double& ll, double& lu, double lo, double hi, double dv,
-                         double dva) {
-          if (fin(lo)) {
-            const double sl = v - lo;
-            const double dla = -ll * (1.0 + dva / sl);
-            const double rc = sigmu - sl * ll - dva * dla;
-            ll += alpha * ((rc - ll * dv) / sl);
-          }
-          if (fin(hi)) {
-            const double su = hi - v;
-            const double dua = -lu * (1.0 - dva / su);
-            const double rc = sigmu - su * lu + dva * dua;
-            lu += alpha * ((rc + lu * dv) / su);
-          }
-          v += alpha * dv;
-        };
-        apply(xi, llx, lux, lox, hix, at.r(k, L::DX), at.r(k, L::DXA));
-        if (ou) apply(ui, llu, luu, lou, hiu, at.r(k, L::DU), at.r(k, L::DUA));
-        pii += alpha * at.r(k, L::DPI);
-        at.r(k, L::X) = xi;
-        at.r(k, L::PI) = pii;
-        at.r(k, L::LL + NU) = llx;
-        at.r(k, L::LU + NU) = lux;
-        if (ou) { at.r(k, L::U) = ui; at.r(k, L::LL) = llu; at.r(k, L::LU) = luu; }
-      }
-      double xa[4], x1a[4], pia[4], ua[2];
-      bcast4(xki, xa);
-      bcast4(xi, x1a);
-      bcast4(pii, pia);
-      ua[0] = qb<0>(ui);
-      ua[1] = qb<1>(ui);
-      StageQ S;
-      S.load(at, k);
-      const double e = resid_q(at, S, k, i, xa, ua, xi);
-      rdyn = fmax(rdyn, fabs(e));
-      double gx, gu[2];
-      grad_q(at, S, k, i, xa, x1a, pia, ua, pii, gx1, gx, gu);
-      // stationarity, complementarity, Sigma of the lane's components
-      double sx = 0.0, sui = 0.0;
-      {
-        double r = gx;
-        if (fin(lox)) { const double sl = xi - lox; sx += llx / sl; musum += sl * llx; r -= llx; }
-        if (fin(hix)) { const double su = hix - xi; sx += lux / su; musum += su * lux; r += lux; }
-        rstat = fmax(rstat, fabs(r));
-        at.r(k, L::GA + NU) = gx;
-      }
-      if (ou) {
-        const double gui = sel2(gu, i);
-        double r = gui;
-        if (fin(lou)) { const double sl = ui - lou; sui += llu / sl; musum += sl * llu; r -= llu; }
-        if (fin(hiu)) { const double su = hiu - ui; sui += luu / su; musum += su * luu; r += luu; }
-        rstat = fmax(rstat, fabs(r));
-        at.r(k, L::GA) = gui;
-      }
-      const double su2[2] = {qb<0>(sui), qb<1>(sui)};
+      if (c.alpha > 0.0 && k > 0) xki += c.alpha * at.r(k - 1, L::DX);
+      StageOutQ o;
+      pass1_stage_q(at, i, k, xki, gx1, c, rstat, rdyn, musum, o);
+      const double su2[2] = {qb<0>(o.sui), qb<1>(o.sui)};
       double P[4], p, K[2][4], kk[2], Gi[3], Kc[2];
-      const bool ok = riccati_q(at, S, k, i, Ph, ph, e, gx, gu, sx, su2, dreg, P, p, K, kk, Gi, Kc);
+      const bool ok = riccati_q(at, o.S, k, i, Ph, ph, o.e, o.gx, o.gu, o.sx, su2, c.dreg, P, p, K,
+                                kk, Gi, Kc);
       pd = pd && ok;
-      store_factor_q(at, k, i, P, p, Kc, kk, Gi, e);
-      gx1 = next_gx1_q(at, S, k, i, pia, ua);
+      store_factor_q(at, k, i, P, p, Kc, kk, Gi, o.e);
+      gx1 = next_gx1_q(at, o.S, k, i, o.pia, o.ua);
     }
     rstat = qmax(rstat);
     rdyn = qmax(rdyn);
     const double mu = mcount > 0.0 ? qsum(musum) / mcount : 0.0;
-    if (!fin(rstat) || !fin(rdyn) || !fin(mu)) {
-      emit_q<T>(a, b, at, i, false, MPCQP_STATUS_NONFINITE, it);
-      return false;
-    }
-    if (!pd) {
-      dreg = dreg > 0.0 ? 8.0 * dreg : (dlast > 0.0 ? dlast : 1e-4);
-      if ((a.strict > 0 && ++ncorr > a.strict) || dreg > 1e12 || it >= max_iter) {
-        emit_q<T>(a, b, at, i, false, MPCQP_STATUS_NOT_CONVEX, it);
-        return false;
-      }
-      alpha = 0.0;
-      continue;
-    }
-    if (dreg > 0.0) {
-      dlast = dreg;
-      dreg = dreg / 3.0 > 1e-12 ? dreg / 3.0 : 0.0;
-    }
-    const bool conv = rstat <= a.tol && rdyn <= a.tol && mu <= a.tol_mu;
-    if (mcount > 0.0 && mu_pol > 0.0 && mu <= mu_pol && rstat <= a.tol_polish &&
-        rdyn <= a.tol_polish) {
+    ipm::Next next = ipm::after_factor(c, a, it, pd, rstat, rdyn, mu, mcount > 0.0);
+    if (next == ipm::kPolish) {
       MPCQP_PCLK(0);
       const bool pol = polish_q<T>(a, at, i, x0i);
       MPCQP_PCLK(4);
@@ -740,85 +817,35 @@ MPCQP_QD bool solve_quad(const Args<T>& a, int b, double* W, bool warm = false,
         emit_q<T>(a, b, at, i, true, MPCQP_STATUS_OPTIMAL, it);
         return true;
       }
-      mu_pol *= 1e-2;
-      alpha = 0.0;
-      if (conv || it >= max_iter) {
-        emit_q<T>(a, b, at, i, false, conv ? MPCQP_STATUS_OPTIMAL : MPCQP_STATUS_MAXITER, it);
-        return false;
-      }
-      continue;
+      next = ipm::after_failed_polish(c, a, it);
     }
-    if (conv || it >= max_iter) {
-      emit_q<T>(a, b, at, i, false, conv ? MPCQP_STATUS_OPTIMAL : MPCQP_STATUS_MAXITER, it);
+    if (next == ipm::kStop) {
+      emit_q<T>(a, b, at, i, false, c.code, it);
       return false;
     }
+    if (next == ipm::kAgain) continue;
 
     MPCQP_PCLK(0);
     // ========================================== pass 2: forward predictor
     double amax = 1.0, c0 = 0.0, c1 = 0.0, c2 = 0.0;
     forward_q(at, N, i, [&](int k, const double (&du)[2], double dxn, const double (&)[4]) {
+      const double dun = sel2(du, i);
       at.r(k, L::DXA) = dxn;
-      if (ou) at.r(k, L::DUA) = sel2(du, i);
-      auto comp = [&](double vj, double dv, double lo, double hi, double l, double lu) {
-        if (fin(lo)) {
-          const double sl = vj - lo;
-          const double dl = -l * (1.0 + dv / sl);
-          if (dv < 0.0) amax = fmin(amax, -sl / dv);
-          if (dl < 0.0) amax = fmin(amax, -l / dl);
-          c0 += sl * l;
-          c1 += sl * dl + l * dv;
-          c2 += dv * dl;
-        }
-        if (fin(hi)) {
-          const double su = hi - vj;
-          const double dl = -lu * (1.0 - dv / su);
-          if (dv > 0.0) amax = fmin(amax, su / dv);
-          if (dl < 0.0) amax = fmin(amax, -lu / dl);
-          c0 += su * lu;
-          c1 += su * dl - lu * dv;
-          c2 -= dv * dl;
-        }
-      };
-      comp(at.r(k, L::X), dxn, at.r(k, L::LO + NU), at.r(k, L::HI + NU),
-           at.r(k, L::LL + NU), at.r(k, L::LU + NU));
-      if (ou)
-        comp(at.r(k, L::U), sel2(du, i), at.r(k, L::LO), at.r(k, L::HI), at.r(k, L::LL),
-             at.r(k, L::LU));
+      if (ou) at.r(k, L::DUA) = dun;
+      pass2_stage_q(at, i, k, dxn, dun, amax, c0, c1, c2);
     });
     amax = qmin(amax);
-    if (mcount > 0.0) {
-      const double mua = (qsum(c0) + amax * (qsum(c1) + amax * qsum(c2))) / mcount;
-      const double r = fmax(0.0, fmin(1.0, mua / mu));
-      sigmu = r * r * r * mu;
-    } else {
-      sigmu = 0.0;
-    }
+    c.sigmu = ipm::centering(mcount, qsum(c0), qsum(c1), qsum(c2), amax, mu);
 
     MPCQP_PCLK(1);
     // ================================ pass 3: backward corrector right side
+    // (the chain stands here inline, not as rhs_step_q: through that call this
+    // kernel's results moved in the last bits)
     {
       double phc = 0.0;
       for (int k = N - 1; k >= 0; --k) {
-        auto rhs = [&](double vj, double dva, double lo, double hi, double l, double lu,
-                       double g) {
-          double s = g;
-          if (fin(lo)) {
-            const double sl = vj - lo;
-            s += (-sigmu - dva * l * (1.0 + dva / sl)) / sl;
-          }
-          if (fin(hi)) {
-            const double su = hi - vj;
-            s += (sigmu - dva * lu * (1.0 - dva / su)) / su;
-          }
-          return s;
-        };
-        const double gx = rhs(at.r(k, L::X), at.r(k, L::DXA), at.r(k, L::LO + NU),
-                              at.r(k, L::HI + NU), at.r(k, L::LL + NU),
-                              at.r(k, L::LU + NU), at.r(k, L::GA + NU));
-        const double gum = ou ? rhs(at.r(k, L::U), at.r(k, L::DUA), at.r(k, L::LO),
-                                    at.r(k, L::HI), at.r(k, L::LL), at.r(k, L::LU),
-                                    at.r(k, L::GA))
-                              : 0.0;
+        double gx, gum;
+        pass3_stage_q(at, i, k, c.sigmu, gx, gum);
         const double gu[2] = {qb<0>(gum), qb<1>(gum)};
         const double p = gx + phc;
         double Pe = p;
@@ -854,36 +881,12 @@ MPCQP_QD bool solve_quad(const Args<T>& a, int b, double* W, bool warm = false,
     // ========================================== pass 4: forward corrector
     amax = 1.0;
     forward_q(at, N, i, [&](int k, const double (&du)[2], double dxn, const double (&dxa)[4]) {
-      double s = at.r(k, L::PV);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s = fma(at.p(k, L::PP, j), dxa[j], s);
-      at.r(k, L::DPI) = s;
+      const double dun = sel2(du, i);
       at.r(k, L::DX) = dxn;
-      if (ou) at.r(k, L::DU) = sel2(du, i);
-      auto comp = [&](double vj, double dv, double dva, double lo, double hi, double l,
-                      double lu) {
-        if (fin(lo)) {
-          const double sl = vj - lo;
-          const double dla = -l * (1.0 + dva / sl);
-          const double dl = (sigmu - sl * l - dva * dla - l * dv) / sl;
-          if (dv < 0.0) amax = fmin(amax, -sl / dv);
-          if (dl < 0.0) amax = fmin(amax, -l / dl);
-        }
-        if (fin(hi)) {
-          const double su = hi - vj;
-          const double dua = -lu * (1.0 - dva / su);
-          const double dl = (sigmu - su * lu + dva * dua + lu * dv) / su;
-          if (dv > 0.0) amax = fmin(amax, su / dv);
-          if (dl < 0.0) amax = fmin(amax, -lu / dl);
-        }
-      };
-      comp(at.r(k, L::X), dxn, at.r(k, L::DXA), at.r(k, L::LO + NU), at.r(k, L::HI + NU),
-           at.r(k, L::LL + NU), at.r(k, L::LU + NU));
-      if (ou)
-        comp(at.r(k, L::U), sel2(du, i), at.r(k, L::DUA), at.r(k, L::LO), at.r(k, L::HI),
-             at.r(k, L::LL), at.r(k, L::LU));
+      if (ou) at.r(k, L::DU) = dun;
+      pass4_stage_q(at, i, k, dxn, dun, dxa, c.sigmu, amax);
     });
-    alpha = fmin(1.0, 0.995 * qmin(amax));
+    c.alpha = ipm::step_length(qmin(amax));
     MPCQP_PCLK(3);
   }
 }

@@ -2,20 +2,24 @@
 // instance on a WHOLE wavefront: the one-launch SQP (sqp_solve.hip) runs each
 // instance in its own single-wave workgroup, where solve_quad kept 60 of the
 // 64 lanes idle while one quad walked the horizon four times per iteration.
-// Here only the serial chains stay on quad 0 (lanes 0..3):
-//   pass 1  the Riccati factorisation (riccati_q, store_factor_q),
-//   pass 2  the predictor's forward sweep (du = K dx + k, dx+ = A dx + B du + e),
+// Here only the serial chains stay serial, behind three functions (factor,
+// forward, rhs: on the fp64 matrix cores, or with -DMPCQP_RICCATI_QUAD on
+// quad 0 with solve_quad's helpers):
+//   pass 1  the Riccati factorisation,
+//   pass 2  the predictor's forward sweep (dx+ = (A + B K) dx + B k + e),
 //   pass 3  the corrector's backward right-hand side (p, Pe, h, k, the cost-to-go),
 //   pass 4  the corrector's forward sweep,
 // and everything per stage runs one quad per stage on the 16 quads of the wave
 // before or after its chain: applying the previous step, the dynamics residual,
-// the gradients, Sigma and the complementarity of pass 1; the step to the
-// boundary and the affine complementarity of pass 2; the corrector right-hand
-// side of pass 3; the costate direction and the step to the boundary of pass 4.
-// Every per-stage quantity is the same expression of the same fields as in
-// solve_quad (the helpers are shared), so the iterates agree with it to the
-// summation order of the wave-wide reductions.  The polish is split the same
-// way (polish_w); the start and the output are solve_quad's (quad 0).  The
+// the gradients, Sigma and the complementarity of pass 1; the input direction,
+// the step to the boundary and the affine complementarity of pass 2; the
+// corrector right-hand side of pass 3; the costate direction and the step to
+// the boundary of pass 4.  Each of these is the function solve_quad calls for
+// the stage (ipm_quad.hpp: pass1..4_stage_q, polish_*_q), and the decisions
+// between the passes are ipm_step.hpp's, so the iterates agree with
+// solve_quad's to the summation order of the wave-wide reductions and of the
+// matrix products.  The polish is split the same way (polish_w); the start
+// and the output are solve_quad's (start_stage_q, emit_q on quad 0).  The
 // QP's workspace in LDS (LD = 1), stage data already staged (stage_in_q).
 //
 // Between the per-stage and the serial parts the values go through the
@@ -307,101 +311,124 @@ MPCQP_QD double du_of_stage(const WsQ<1>& at, int k, int i) {
 }
 
 // The backward sweep of a right-hand side on the stored factorisation (quad
-// 0; pass 3 of the interior point, solve_quad's expressions): g_x row i from
-// field FGX (lane-relative), g_u (both inputs) from FGU; writes k -> KV and
-// p -> PV (each stage's fields are read before they are written).
+// 0; the chain of pass 3, ipmq::rhs_step_q): g_x row i from field FGX
+// (lane-relative), g_u (both inputs) from FGU; writes k -> KV and p -> PV
+// (each stage's fields are read before they are written).
 template <int FGX, int FGU>
 MPCQP_QD void rhs_sweep_q(const WsQ<1>& at, int N, int i) {
-  const bool ou = i < NU;
   double phc = 0.0;
   for (int k = N - 1; k >= 0; --k) {
-    const double gx = at.r(k, FGX);
     const double gu[2] = {at(k, FGU), at(k, FGU + 1)};
-    const double p = gx + phc;
-    double Pe = p;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) Pe = fma(at.p(k, L::PP, j), at(k, L::E + j), Pe);
-    double Pea[4];
-    bcast4(Pe, Pea);
-    double h[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      double s = gu[r];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) s = fma(at(k, L::DB + q * NU + r), Pea[q], s);
-      h[r] = s;
-    }
-    const double Gi[3] = {at(k, L::GI + 0), at(k, L::GI + 1), at(k, L::GI + 2)};
-    double kk[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) kk[r] = -(Gi[pk(r, 0)] * h[0] + Gi[pk(r, 1)] * h[1]);
-    if (ou) at.r(k, L::KV) = sel2(kk, i);
-    double s = 0.0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) s = fma(at.r(k, L::DA + q * NX), Pea[q], s);
-#pragma unroll
-    for (int r = 0; r < 2; ++r) s = fma(at.r(k, L::KM + r * NX), h[r], s);
-    phc = s;
-    at.r(k, L::PV) = p;
+    rhs_step_q(at, i, k, at.r(k, FGX), gu, phc);
   }
 }
 
+// ------------------------------------------------------- the serial chains
+// The three recursions over the horizon, on the matrix cores or
+// (-DMPCQP_RICCATI_QUAD, the A/B build) on quad 0 with ipm_quad.hpp's helpers.
+// All 64 lanes call them; the caller synchronises the workspace before and
+// after.  qd = the lane's quad, i = its lane in the quad.
+//
+// factor   the Riccati factorisation from e in E, g_x in FGX (lane-relative),
+//          g_u in FGU, FGU+1, Sigma_x in FSX (lane-relative), Sigma_u in FSU,
+//          FSU+1 -> PP, KM, GI, KV, PV; wave-uniform: every pivot positive.
+template <int FGX, int FGU, int FSX, int FSU>
+MPCQP_QD bool factor(const WsQ<1>& at, int N, int qd, int i, double dreg) {
+#ifndef MPCQP_RICCATI_QUAD
+  return riccati_mfma<FGX, FGU, FSX, FSU>(at.W, N, dreg);
+#else
+  bool pd = true;
+  if (qd == 0) {
+    double Ph[4] = {0.0, 0.0, 0.0, 0.0}, ph = 0.0;
+    for (int k = N - 1; k >= 0; --k) {
+      StageQ S;
+      S.load(at, k);
+      const double e = at.r(k, L::E), gx = at.r(k, FGX), sx = at.r(k, FSX);
+      const double gu[2] = {at(k, FGU), at(k, FGU + 1)};
+      const double su2[2] = {at(k, FSU), at(k, FSU + 1)};
+      double P[4], p, K[2][4], kk[2], Gi[3], Kc[2];
+      pd = riccati_q(at, S, k, i, Ph, ph, e, gx, gu, sx, su2, dreg, P, p, K, kk, Gi, Kc) && pd;
+      store_factor_q(at, k, i, P, p, Kc, kk, Gi, e);
+    }
+  }
+  return from_lane0(pd);
+#endif
+}
+
+// rhs      a right-hand side on the stored factorisation: g_x in FGX, g_u in
+//          FGU, FGU+1 -> p in PV, k in KV.
+template <int FGX, int FGU>
+MPCQP_QD void rhs(const WsQ<1>& at, int N, int qd, int i) {
+#ifndef MPCQP_RICCATI_QUAD
+  rhs_mfma<FGX, FGU>(at.W, N);
+  wave_lds_sync();
+  // (g_u may be in KV: every stage reads its own before writing k there)
+  for (int k = qd; k < N; k += kQuads) rhs_kk_stage<FGU>(at, k, i);
+#else
+  if (qd == 0) rhs_sweep_q<FGX, FGU>(at, N, i);
+#endif
+}
+
+// forward  the state direction of x_{k+1} -> the lane-relative field FDX of
+//          stage k; the input direction of a stage is du_of_stage<FDX>.
+template <int FDX>
+MPCQP_QD void forward(const WsQ<1>& at, int N, int qd, int i) {
+#ifndef MPCQP_RICCATI_QUAD
+  forward_mfma<FDX>(at.W, N);
+#else
+  if (qd == 0)
+    forward_q(at, N, i, [&](int k, const double (&)[2], double dxn, const double (&)[4]) {
+      at.r(k, FDX) = dxn;
+    });
+#endif
+}
+
+// What stage k needs from the stage after it: A_{k+1}'pi_{k+2} + H2xu_{k+1}
+// u_{k+1}, row i, from that stage's pi in FPI and u in FU, each plus alpha
+// times FDPI / FDU when alpha > 0 (its step not yet applied); 0 at the last
+// stage.
+template <int FPI, int FU, int FDPI, int FDU>
+MPCQP_QD double later_gx1(const WsQ<1>& at, int N, int i, int k, double alpha) {
+  if (k + 1 >= N) return 0.0;
+  const bool ou = i < NU;
+  double pin = at.r(k + 1, FPI), un = ou ? at.r(k + 1, FU) : 0.0;
+  if (alpha > 0.0) {
+    pin += alpha * at.r(k + 1, FDPI);
+    if (ou) un += alpha * at.r(k + 1, FDU);
+  }
+  double pia[4], ua[2];
+  bcast4(pin, pia);
+  ua[0] = qb<0>(un);
+  ua[1] = qb<1>(un);
+  StageQ S;
+  return next_gx1_q(at, S, k + 1, i, pia, ua);
+}
+
 // polish_q (ipm_quad.hpp) on the whole wave: each method-of-multipliers step
-// is the per-stage residual / gradient / penalty (one quad per stage, into
-// the factor fields the serial sweep overwrites after reading: e -> E, g_x ->
-// PV, g_u -> KV, the penalties -> KM / GI), the Riccati sweep on quad 0, the
-// forward sweep on quad 0 (the state direction of stage k -> E, the iterate
-// updated), then per stage the costate update, the multipliers and the
-// active-set tests.  Same expressions as polish_q; returns (wave-uniform)
-// whether the polish certified its vertex.
+// is the per-stage residual / gradient / penalty (one quad per
+// stage, into the factor fields the serial sweep overwrites after reading: e
+// -> E, g_x -> PV, g_u -> KV, the penalties -> KM / GI), the Riccati sweep
+// (factor; rhs where the factors stand), the forward sweep (the state
+// direction of stage k -> E), then per stage the step, the costate update, the
+// multipliers and the active-set tests (polish_check_q).  Returns
+// (wave-uniform) whether the polish certified its vertex.
 template <typename T>
 MPCQP_QD bool polish_w(const Args<T>& a, const WsQ<1>& at, int qd, int i, double x0i,
                        bool warm) {
   const int N = a.N;
   const bool ou = i < NU;
-#ifdef MPCQP_RICCATI_QUAD
-  const bool q0 = qd == 0;
-#endif
-  for (int k = qd; k < N; k += kQuads) {
-#pragma unroll
-    for (int part = 0; part < 2; ++part) {
-      if (part == 1 && !ou) continue;
-      const int j = part == 0 ? NU + i : i;
-      const double vj = part == 0 ? at.r(k, L::X) : at.r(k, L::U);
-      double y = 0.0;
-      if (!warm) {
-        const double lo = at(k, L::LO + j), hi = at(k, L::HI + j);
-        const double l = at(k, L::LL + j), u = at(k, L::LU + j);
-        const double rl = fin(lo) ? l / (vj - lo) : 0.0;
-        const double ru = fin(hi) ? u / (hi - vj) : 0.0;
-        const double act = (ru > 1.0 && ru >= rl) ? 1.0 : ((rl > 1.0) ? -1.0 : 0.0);
-        at(k, L::GA + j) = act;
-        y = act > 0.0 ? u : (act < 0.0 ? -l : 0.0);
-      }
-      if (part == 1) { at.r(k, L::DU) = vj; at.r(k, L::DUA) = y; }
-      else { at.r(k, L::DX) = vj; at.r(k, L::DXA) = y; }
-    }
-    at.r(k, L::DPI) = at.r(k, L::PI);
-  }
+  for (int k = qd; k < N; k += kQuads) polish_init_q(at, i, k, warm);
   wave_lds_sync();
-  constexpr int kSteps = 4, kRounds = 4;
-#ifdef MPCQP_POLISH_EARLY
-  constexpr int kPolishEarly = MPCQP_POLISH_EARLY;
-#else
-  constexpr int kPolishEarly = kSteps;
-#endif
-#ifdef MPCQP_WARM_ROUNDS
-  const int rounds = warm ? MPCQP_WARM_ROUNDS : kRounds;
-#else
-  const int rounds = kRounds;
-#endif
+  const int rounds = polish_rounds(warm);
   for (int round = 0; round < rounds; ++round) {
     bool good = true, changed = false;
-    for (int step = 0; step < kSteps; ++step) {
-      const double rho = step == 0 ? 1e8 : (step == 1 ? 1e6 : 1e4);
+    for (int step = 0; step < kPolishSteps; ++step) {
+      const double rho = polish_rho(step);
       // the last step keeps the penalty of the one before: same factorisation
       const bool refactor = step < 3;
       // per stage: residual, gradients and the active components' penalty
+      // (polish_grad_q's statements on their own text: as that call, this
+      // kernel measured 0.8 % slower)
       for (int k = qd; k < N; k += kQuads) {
         const double xi = at.r(k, L::DX), pii = at.r(k, L::DPI);
         const double ui = ou ? at.r(k, L::DU) : 0.0;
@@ -457,19 +484,12 @@ MPCQP_QD bool polish_w(const Args<T>& a, const WsQ<1>& at, int qd, int i, double
         }
       }
       wave_lds_sync();
-#ifndef MPCQP_RICCATI_QUAD
-      if (refactor) {
-        good = riccati_mfma<L::PV, L::KV, L::KM, L::GI>(at.W, N, 0.0) && good;
-      } else {
-        // the penalty and the active set of the previous step: its factors
-        // stand, only the right-hand side is swept (e back in E first)
-        rhs_mfma<L::PV, L::KV>(at.W, N);
-        wave_lds_sync();
-        // (g_u is in KV: every stage reads its own before writing k there)
-        for (int k = qd; k < N; k += kQuads) rhs_kk_stage<L::KV>(at, k, i);
-      }
+      // the penalty and the active set of the previous step: its factors
+      // stand, only the right-hand side is swept
+      if (refactor) good = factor<L::PV, L::KV, L::KM, L::GI>(at, N, qd, i, 0.0) && good;
+      else rhs<L::PV, L::KV>(at, N, qd, i);
       wave_lds_sync();
-      forward_mfma<L::E>(at.W, N);
+      forward<L::E>(at, N, qd, i);
       wave_lds_sync();
       // the step: x, u += the directions (the state direction of stage k is
       // in E(k); du_k needs that of stage k-1, so the updates of DX follow)
@@ -477,74 +497,14 @@ MPCQP_QD bool polish_w(const Args<T>& a, const WsQ<1>& at, int qd, int i, double
         if (ou) at.r(k, L::DU) += du_of_stage<L::E>(at, k, i);
       wave_lds_sync();
       for (int k = qd; k < N; k += kQuads) at.r(k, L::DX) += at.r(k, L::E);
-#else
-      if (q0 && refactor) {
-        double Ph[4] = {0.0, 0.0, 0.0, 0.0}, ph = 0.0;
-        for (int k = N - 1; k >= 0; --k) {
-          StageQ S;
-          S.load(at, k);
-          const double e = at.r(k, L::E), gx = at.r(k, L::PV), sx = at.r(k, L::KM);
-          const double gu[2] = {at(k, L::KV), at(k, L::KV + 1)};
-          const double su2[2] = {at(k, L::GI), at(k, L::GI + 1)};
-          double P[4], p, K[2][4], kk[2], Gi[3], Kc[2];
-          good = riccati_q(at, S, k, i, Ph, ph, e, gx, gu, sx, su2, 0.0, P, p, K, kk, Gi, Kc) && good;
-          store_factor_q(at, k, i, P, p, Kc, kk, Gi, e);
-        }
-      } else if (q0) {
-        rhs_sweep_q<L::PV, L::KV>(at, N, i);
-      }
-      if (q0) {
-        forward_q(at, N, i, [&](int k, const double (&du)[2], double dxn, const double (&)[4]) {
-          at.r(k, L::E) = dxn;
-          at.r(k, L::DX) += dxn;
-          if (ou) at.r(k, L::DU) += sel2(du, i);
-        });
-      }
-#endif
       wave_lds_sync();
-      const bool last = step == kSteps - 1;
+      const bool last = step == kPolishSteps - 1;
       const bool probe = !last && step >= kPolishEarly;
       bool pass = true;
       for (int k = qd; k < N; k += kQuads) {
-        double s = at.r(k, L::PV);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s = fma(at.p(k, L::PP, j), at(k, L::E + j), s);
-        at.r(k, L::DPI) += s;
-#pragma unroll
-        for (int part = 0; part < 2; ++part) {
-          if (part == 1 && !ou) continue;
-          const int j = part == 0 ? NU + i : i;
-          const double vj = part == 0 ? at.r(k, L::DX) : at.r(k, L::DU);
-          const double lo = at(k, L::LO + j), hi = at(k, L::HI + j);
-          const double act = at(k, L::GA + j);
-          if (act != 0.0) {
-            double& yr = part == 0 ? at.r(k, L::DXA) : at.r(k, L::DUA);
-            const double bnd = act > 0.0 ? hi : lo;
-            const double y = yr + rho * (vj - bnd);
-            yr = y;
-            if (probe)
-              pass = pass && fabs(vj - bnd) <= 1e-9 * (1.0 + fabs(bnd)) &&
-                     !(act > 0.0 ? y < -1e-9 * (1.0 + fabs(y)) : y > 1e-9 * (1.0 + fabs(y)));
-            if (last) {
-              good = good && fabs(vj - bnd) <= 1e-9 * (1.0 + fabs(bnd));
-              if (act > 0.0 ? y < -1e-9 * (1.0 + fabs(y)) : y > 1e-9 * (1.0 + fabs(y))) {
-                at(k, L::GA + j) = 0.0;
-                yr = 0.0;
-                changed = true;
-              }
-            }
-          } else if (last || probe) {
-            const double jl = (lo - vj) / (1.0 + fabs(lo));
-            const double jh = (vj - hi) / (1.0 + fabs(hi));
-            if (jl > 1e-9 || jh > 1e-9) {
-              if (last) {
-                at(k, L::GA + j) = jl > jh ? -1.0 : 1.0;
-                changed = true;
-              }
-              pass = false;
-            }
-          }
-        }
+        const double dxa[4] = {at(k, L::E + 0), at(k, L::E + 1), at(k, L::E + 2), at(k, L::E + 3)};
+        polish_check_q(at, i, k, dxa, at.r(k, L::DX), ou ? at.r(k, L::DU) : 0.0, rho, last, probe,
+                       good, changed, pass);
       }
       wave_lds_sync();
       if (probe && wave_min(good && pass ? 1.0 : 0.0) > 0.5) return true;
@@ -570,45 +530,14 @@ MPCQP_QD bool solve_wave(const Args<T>& a, int b, double* W, bool warm = false,
   const bool q0 = qd == 0;
   const WsQ<1> at(W, i);
   const bool ou = i < NU;
-  const int N = a.N, nx = a.nx, nu = a.nu;
-  const double x0i = i < nx ? (double)a.x0[(int64_t)b * a.sX0 + i] : 0.0;
+  const int N = a.N;
+  const double x0i = i < a.nx ? (double)a.x0[(int64_t)b * a.sX0 + i] : 0.0;
 
   // ------------------------------------------------- start (quad 0, serial)
   double mc = 0.0;
   if (q0) {
     double xi = x0i;
-    for (int k = 0; k < N; ++k) {
-      const double ci = at.r(k, L::DC);
-      double ui = 0.0;
-      if (ou) {
-        const double u0 =
-            (a.U0 && i < nu) ? (double)a.U0[(int64_t)b * a.sU0 + (int64_t)k * nu + i] : 0.0;
-        ui = interior(u0, at.r(k, L::LO), at.r(k, L::HI));
-        at.r(k, L::U) = ui;
-      }
-      double xa[4], ua[2];
-      bcast4(xi, xa);
-      ua[0] = qb<0>(ui);
-      ua[1] = qb<1>(ui);
-      double s = ci;
-#pragma unroll
-      for (int j = 0; j < NX; ++j) s = fma(at.ra(k, L::DA + j), xa[j], s);
-#pragma unroll
-      for (int r = 0; r < NU; ++r) s = fma(at.rb(k, L::DB + r), ua[r], s);
-      const double lox = at.r(k, L::LO + NU), hix = at.r(k, L::HI + NU);
-      xi = interior(s, lox, hix);
-      at.r(k, L::X) = xi;
-      at.r(k, L::PI) = 0.0;
-      at.r(k, L::LL + NU) = fin(lox) ? 1.0 : 0.0;
-      at.r(k, L::LU + NU) = fin(hix) ? 1.0 : 0.0;
-      mc += (fin(lox) ? 1.0 : 0.0) + (fin(hix) ? 1.0 : 0.0);
-      if (ou) {
-        const double lou = at.r(k, L::LO), hiu = at.r(k, L::HI);
-        at.r(k, L::LL) = fin(lou) ? 1.0 : 0.0;
-        at.r(k, L::LU) = fin(hiu) ? 1.0 : 0.0;
-        mc += (fin(lou) ? 1.0 : 0.0) + (fin(hiu) ? 1.0 : 0.0);
-      }
-    }
+    for (int k = 0; k < N; ++k) start_stage_q(a, b, at, i, k, xi, mc);
   }
   const double mcount = wsum(mc);
   wave_lds_sync();
@@ -622,11 +551,8 @@ MPCQP_QD bool solve_wave(const Args<T>& a, int b, double* W, bool warm = false,
     }
   }
 
-  double alpha = 0.0, sigmu = 0.0;
-  double mu_pol = a.mu_polish;
-  double dreg = 0.0, dlast = 0.0;
-  int ncorr = 0;
-  const int max_iter = a.max_iter;
+  ipm::Control c;
+  c.mu_pol = a.mu_polish;
   for (int it = 0;; ++it) {
     // ========================= pass 1a: per stage, the neighbours' values
     // x_k after the previous step (stage k-1's state, not yet updated in
@@ -634,21 +560,8 @@ MPCQP_QD bool solve_wave(const Args<T>& a, int b, double* W, bool warm = false,
     // after the step -> PV
     for (int k = qd; k < N; k += kQuads) {
       double xki = k == 0 ? x0i : at.r(k - 1, L::X);
-      if (alpha > 0.0 && k > 0) xki += alpha * at.r(k - 1, L::DX);
-      double gx1 = 0.0;
-      if (k + 1 < N) {
-        double pin = at.r(k + 1, L::PI), un = ou ? at.r(k + 1, L::U) : 0.0;
-        if (alpha > 0.0) {
-          pin += alpha * at.r(k + 1, L::DPI);
-          if (ou) un += alpha * at.r(k + 1, L::DU);
-        }
-        double pia[4], ua[2];
-        bcast4(pin, pia);
-        ua[0] = qb<0>(un);
-        ua[1] = qb<1>(un);
-        StageQ S;
-        gx1 = next_gx1_q(at, S, k + 1, i, pia, ua);
-      }
+      if (c.alpha > 0.0 && k > 0) xki += c.alpha * at.r(k - 1, L::DX);
+      const double gx1 = later_gx1<L::PI, L::U, L::DPI, L::DU>(at, N, i, k, c.alpha);
       at.r(k, L::E) = xki;
       at.r(k, L::PV) = gx1;
     }
@@ -657,120 +570,23 @@ MPCQP_QD bool solve_wave(const Args<T>& a, int b, double* W, bool warm = false,
     // ============ pass 1b: per stage, the step, residual, gradients, Sigma
     double rstat = 0.0, rdyn = 0.0, musum = 0.0;
     for (int k = qd; k < N; k += kQuads) {
-      double xi = at.r(k, L::X), pii = at.r(k, L::PI);
-      double llx = at.r(k, L::LL + NU), lux = at.r(k, L::LU + NU);
-      double ui = 0.0, llu = 0.0, luu = 0.0;
-      if (ou) { ui = at.r(k, L::U); llu = at.r(k, L::LL); luu = at.r(k, L::LU); }
-      const double lox = at.r(k, L::LO + NU), hix = at.r(k, L::HI + NU);
-      const double lou = ou ? at.r(k, L::LO) : -kInf, hiu = ou ? at.r(k, L::HI) : kInf;
-      const double xki = at.r(k, L::E), gx1 = at.r(k, L::PV);
-      if (alpha > 0.0) {  // apply the corrector step of the previous iteration
-        auto apply = [&](double& v, double& ll, double& lu, double lo, double hi, double dv,
-                         double dva) {
-          if (fin(lo)) {
-            const double sl = v - lo;
-            const double dla = -ll * (1.0 + dva / sl);
-            const double rc = sigmu - sl * ll - dva * dla;
-            ll += alpha * ((rc - ll * dv) / sl);
-          }
-          if (fin(hi)) {
-            const double su = hi - v;
-            const double dua = -lu * (1.0 - dva / su);
-            const double rc = sigmu - su * lu + dva * dua;
-            lu += alpha * ((rc + lu * dv) / su);
-          }
-          v += alpha * dv;
-        };
-        apply(xi, llx, lux, lox, hix, at.r(k, L::DX), at.r(k, L::DXA));
-        if (ou) apply(ui, llu, luu, lou, hiu, at.r(k, L::DU), at.r(k, L::DUA));
-        pii += alpha * at.r(k, L::DPI);
-        at.r(k, L::X) = xi;
-        at.r(k, L::PI) = pii;
-        at.r(k, L::LL + NU) = llx;
-        at.r(k, L::LU + NU) = lux;
-        if (ou) { at.r(k, L::U) = ui; at.r(k, L::LL) = llu; at.r(k, L::LU) = luu; }
-      }
-      double xa[4], x1a[4], pia[4], ua[2];
-      bcast4(xki, xa);
-      bcast4(xi, x1a);
-      bcast4(pii, pia);
-      ua[0] = qb<0>(ui);
-      ua[1] = qb<1>(ui);
-      StageQ S;
-      S.load(at, k);
-      const double e = resid_q(at, S, k, i, xa, ua, xi);
-      rdyn = fmax(rdyn, fabs(e));
-      double gx, gu[2];
-      grad_q(at, S, k, i, xa, x1a, pia, ua, pii, gx1, gx, gu);
-      double sx = 0.0, sui = 0.0;
-      {
-        double r = gx;
-        if (fin(lox)) { const double sl = xi - lox; sx += llx / sl; musum += sl * llx; r -= llx; }
-        if (fin(hix)) { const double su = hix - xi; sx += lux / su; musum += su * lux; r += lux; }
-        rstat = fmax(rstat, fabs(r));
-        at.r(k, L::GA + NU) = gx;
-      }
-      if (ou) {
-        const double gui = sel2(gu, i);
-        double r = gui;
-        if (fin(lou)) { const double sl = ui - lou; sui += llu / sl; musum += sl * llu; r -= llu; }
-        if (fin(hiu)) { const double su = hiu - ui; sui += luu / su; musum += su * luu; r += luu; }
-        rstat = fmax(rstat, fabs(r));
-        at.r(k, L::GA) = gui;
-        at.r(k, L::DUA) = sui;
-      }
-      at.r(k, L::E) = e;
-      at.r(k, L::DXA) = sx;
+      StageOutQ o;
+      pass1_stage_q(at, i, k, at.r(k, L::E), at.r(k, L::PV), c, rstat, rdyn, musum, o);
+      if (ou) at.r(k, L::DUA) = o.sui;
+      at.r(k, L::E) = o.e;
+      at.r(k, L::DXA) = o.sx;
     }
     wave_lds_sync();
     MPCQP_PCLK(9);
-    // ==================== pass 1c: the Riccati factorisation (quad 0, serial)
-    bool pd = true;
-#ifndef MPCQP_RICCATI_QUAD
-    pd = riccati_mfma<L::GA + NU, L::GA, L::DXA, L::DUA>(W, N, dreg);
-#else
-    if (q0) {
-      double Ph[4] = {0.0, 0.0, 0.0, 0.0}, ph = 0.0;
-      for (int k = N - 1; k >= 0; --k) {
-        StageQ S;
-        S.load(at, k);
-        const double e = at.r(k, L::E), gx = at.r(k, L::GA + NU), sx = at.r(k, L::DXA);
-        const double gu[2] = {at(k, L::GA), at(k, L::GA + 1)};
-        const double su2[2] = {at(k, L::DUA), at(k, L::DUA + 1)};
-        double P[4], p, K[2][4], kk[2], Gi[3], Kc[2];
-        const bool ok = riccati_q(at, S, k, i, Ph, ph, e, gx, gu, sx, su2, dreg, P, p, K, kk, Gi, Kc);
-        pd = pd && ok;
-        store_factor_q(at, k, i, P, p, Kc, kk, Gi, e);
-      }
-    }
-    pd = from_lane0(pd);
-#endif
+    // ============================== pass 1c: the Riccati factorisation
+    const bool pd = factor<L::GA + NU, L::GA, L::DXA, L::DUA>(at, N, qd, i, c.dreg);
     MPCQP_PCLK(10);
     rstat = wave_max(rstat);
     rdyn = wave_max(rdyn);
     const double mu = mcount > 0.0 ? wsum(musum) / mcount : 0.0;
     wave_lds_sync();
-    if (!fin(rstat) || !fin(rdyn) || !fin(mu)) {
-      if (q0) emit_q<T>(a, b, at, i, false, MPCQP_STATUS_NONFINITE, it);
-      return false;
-    }
-    if (!pd) {
-      dreg = dreg > 0.0 ? 8.0 * dreg : (dlast > 0.0 ? dlast : 1e-4);
-      if ((a.strict > 0 && ++ncorr > a.strict) || dreg > 1e12 || it >= max_iter) {
-        if (q0) emit_q<T>(a, b, at, i, false, MPCQP_STATUS_NOT_CONVEX, it);
-        return false;
-      }
-      MPCQP_PCLK(5);
-      alpha = 0.0;
-      continue;
-    }
-    if (dreg > 0.0) {
-      dlast = dreg;
-      dreg = dreg / 3.0 > 1e-12 ? dreg / 3.0 : 0.0;
-    }
-    const bool conv = rstat <= a.tol && rdyn <= a.tol && mu <= a.tol_mu;
-    if (mcount > 0.0 && mu_pol > 0.0 && mu <= mu_pol && rstat <= a.tol_polish &&
-        rdyn <= a.tol_polish) {
+    ipm::Next next = ipm::after_factor(c, a, it, pd, rstat, rdyn, mu, mcount > 0.0);
+    if (next == ipm::kPolish) {
       MPCQP_PCLK(0);
       const bool pol = polish_w<T>(a, at, qd, i, x0i, false);
       MPCQP_PCLK(4);
@@ -778,155 +594,54 @@ MPCQP_QD bool solve_wave(const Args<T>& a, int b, double* W, bool warm = false,
         if (q0) emit_q<T>(a, b, at, i, true, MPCQP_STATUS_OPTIMAL, it);
         return true;
       }
-      mu_pol *= 1e-2;
-      alpha = 0.0;
-      if (conv || it >= max_iter) {
-        if (q0) emit_q<T>(a, b, at, i, false, conv ? MPCQP_STATUS_OPTIMAL : MPCQP_STATUS_MAXITER, it);
-        return false;
-      }
-      continue;
+      next = ipm::after_failed_polish(c, a, it);
+    } else if (next == ipm::kAgain) {
+      MPCQP_PCLK(5);
     }
-    if (conv || it >= max_iter) {
-      if (q0) emit_q<T>(a, b, at, i, false, conv ? MPCQP_STATUS_OPTIMAL : MPCQP_STATUS_MAXITER, it);
+    if (next == ipm::kStop) {
+      if (q0) emit_q<T>(a, b, at, i, false, c.code, it);
       return false;
     }
+    if (next == ipm::kAgain) continue;
 
     MPCQP_PCLK(0);
-    // ============ pass 2: the predictor's forward sweep (quad 0), then per stage
-#ifndef MPCQP_RICCATI_QUAD
-    forward_mfma<L::DXA>(W, N);
+    // ============ pass 2: the predictor's forward sweep, then per stage
+    forward<L::DXA>(at, N, qd, i);
     wave_lds_sync();
-#else
-    if (q0)
-      forward_q(at, N, i, [&](int k, const double (&du)[2], double dxn, const double (&)[4]) {
-        at.r(k, L::DXA) = dxn;
-        if (ou) at.r(k, L::DUA) = sel2(du, i);
-      });
-    wave_lds_sync();
-#endif
     double amax = 1.0, c0 = 0.0, c1 = 0.0, c2 = 0.0;
     for (int k = qd; k < N; k += kQuads) {
-#ifndef MPCQP_RICCATI_QUAD
-      if (ou) at.r(k, L::DUA) = du_of_stage<L::DXA>(at, k, i);
-#endif
-      auto comp = [&](double vj, double dv, double lo, double hi, double l, double lu) {
-        if (fin(lo)) {
-          const double sl = vj - lo;
-          const double dl = -l * (1.0 + dv / sl);
-          if (dv < 0.0) amax = fmin(amax, -sl / dv);
-          if (dl < 0.0) amax = fmin(amax, -l / dl);
-          c0 += sl * l;
-          c1 += sl * dl + l * dv;
-          c2 += dv * dl;
-        }
-        if (fin(hi)) {
-          const double su = hi - vj;
-          const double dl = -lu * (1.0 - dv / su);
-          if (dv > 0.0) amax = fmin(amax, su / dv);
-          if (dl < 0.0) amax = fmin(amax, -lu / dl);
-          c0 += su * lu;
-          c1 += su * dl - lu * dv;
-          c2 -= dv * dl;
-        }
-      };
-      comp(at.r(k, L::X), at.r(k, L::DXA), at.r(k, L::LO + NU), at.r(k, L::HI + NU),
-           at.r(k, L::LL + NU), at.r(k, L::LU + NU));
-      if (ou)
-        comp(at.r(k, L::U), at.r(k, L::DUA), at.r(k, L::LO), at.r(k, L::HI), at.r(k, L::LL),
-             at.r(k, L::LU));
+      const double dun = ou ? du_of_stage<L::DXA>(at, k, i) : 0.0;
+      if (ou) at.r(k, L::DUA) = dun;
+      pass2_stage_q(at, i, k, at.r(k, L::DXA), dun, amax, c0, c1, c2);
     }
     amax = wave_min(amax);
-    if (mcount > 0.0) {
-      const double mua = (wsum(c0) + amax * (wsum(c1) + amax * wsum(c2))) / mcount;
-      const double r = fmax(0.0, fmin(1.0, mua / mu));
-      sigmu = r * r * r * mu;
-    } else {
-      sigmu = 0.0;
-    }
+    c.sigmu = ipm::centering(mcount, wsum(c0), wsum(c1), wsum(c2), amax, mu);
 
     MPCQP_PCLK(1);
     // ==== pass 3: per stage the corrector right-hand side (-> GA), then the
-    // backward chain (quad 0)
+    // backward chain
     for (int k = qd; k < N; k += kQuads) {
-      auto rhs = [&](double vj, double dva, double lo, double hi, double l, double lu, double g) {
-        double s = g;
-        if (fin(lo)) {
-          const double sl = vj - lo;
-          s += (-sigmu - dva * l * (1.0 + dva / sl)) / sl;
-        }
-        if (fin(hi)) {
-          const double su = hi - vj;
-          s += (sigmu - dva * lu * (1.0 - dva / su)) / su;
-        }
-        return s;
-      };
-      const double gx = rhs(at.r(k, L::X), at.r(k, L::DXA), at.r(k, L::LO + NU),
-                            at.r(k, L::HI + NU), at.r(k, L::LL + NU), at.r(k, L::LU + NU),
-                            at.r(k, L::GA + NU));
-      if (ou) {
-        const double gum = rhs(at.r(k, L::U), at.r(k, L::DUA), at.r(k, L::LO), at.r(k, L::HI),
-                               at.r(k, L::LL), at.r(k, L::LU), at.r(k, L::GA));
-        at.r(k, L::GA) = gum;
-      }
+      double gx, gum;
+      pass3_stage_q(at, i, k, c.sigmu, gx, gum);
+      if (ou) at.r(k, L::GA) = gum;
       at.r(k, L::GA + NU) = gx;
     }
     wave_lds_sync();
-#ifndef MPCQP_RICCATI_QUAD
-    rhs_mfma<L::GA + NU, L::GA>(W, N);
-    wave_lds_sync();
-    for (int k = qd; k < N; k += kQuads) rhs_kk_stage<L::GA>(at, k, i);
-#else
-    if (q0) rhs_sweep_q<L::GA + NU, L::GA>(at, N, i);
-#endif
+    rhs<L::GA + NU, L::GA>(at, N, qd, i);
     wave_lds_sync();
 
     MPCQP_PCLK(2);
-    // ========== pass 4: the corrector's forward sweep (quad 0), then per stage
-#ifndef MPCQP_RICCATI_QUAD
-    forward_mfma<L::DX>(W, N);
+    // ========== pass 4: the corrector's forward sweep, then per stage
+    forward<L::DX>(at, N, qd, i);
     wave_lds_sync();
-#else
-    if (q0)
-      forward_q(at, N, i, [&](int k, const double (&du)[2], double dxn, const double (&)[4]) {
-        at.r(k, L::DX) = dxn;
-        if (ou) at.r(k, L::DU) = sel2(du, i);
-      });
-    wave_lds_sync();
-#endif
     amax = 1.0;
     for (int k = qd; k < N; k += kQuads) {
-#ifndef MPCQP_RICCATI_QUAD
-      if (ou) at.r(k, L::DU) = du_of_stage<L::DX>(at, k, i);
-#endif
-      const double dxn = at.r(k, L::DX);
-      double s = at.r(k, L::PV);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s = fma(at.p(k, L::PP, j), at(k, L::DX + j), s);
-      at.r(k, L::DPI) = s;
-      auto comp = [&](double vj, double dv, double dva, double lo, double hi, double l,
-                      double lu) {
-        if (fin(lo)) {
-          const double sl = vj - lo;
-          const double dla = -l * (1.0 + dva / sl);
-          const double dl = (sigmu - sl * l - dva * dla - l * dv) / sl;
-          if (dv < 0.0) amax = fmin(amax, -sl / dv);
-          if (dl < 0.0) amax = fmin(amax, -l / dl);
-        }
-        if (fin(hi)) {
-          const double su = hi - vj;
-          const double dua = -lu * (1.0 - dva / su);
-          const double dl = (sigmu - su * lu + dva * dua + lu * dv) / su;
-          if (dv > 0.0) amax = fmin(amax, su / dv);
-          if (dl < 0.0) amax = fmin(amax, -lu / dl);
-        }
-      };
-      comp(at.r(k, L::X), dxn, at.r(k, L::DXA), at.r(k, L::LO + NU), at.r(k, L::HI + NU),
-           at.r(k, L::LL + NU), at.r(k, L::LU + NU));
-      if (ou)
-        comp(at.r(k, L::U), at.r(k, L::DU), at.r(k, L::DUA), at.r(k, L::LO), at.r(k, L::HI),
-             at.r(k, L::LL), at.r(k, L::LU));
+      const double dun = ou ? du_of_stage<L::DX>(at, k, i) : 0.0;
+      if (ou) at.r(k, L::DU) = dun;
+      const double dxa[4] = {at(k, L::DX + 0), at(k, L::DX + 1), at(k, L::DX + 2), at(k, L::DX + 3)};
+      pass4_stage_q(at, i, k, at.r(k, L::DX), dun, dxa, c.sigmu, amax);
     }
-    alpha = fmin(1.0, 0.995 * wave_min(amax));
+    c.alpha = ipm::step_length(wave_min(amax));
     wave_lds_sync();
     MPCQP_PCLK(3);
   }

@@ -10,8 +10,10 @@ import numpy as np
 import pytest
 import torch
 
+import _ipm_cases as ic
 from model_predictive_control_amd import batched
-from model_predictive_control_amd._native import STATUS_POLISHED
+from model_predictive_control_amd._native import (STATUS_MAXITER, STATUS_NONFINITE,
+                                                  STATUS_NOT_CONVEX, STATUS_POLISHED)
 from model_predictive_control_amd.parameters import VehicleParameters
 from oracle import condense as oc
 from oracle import qp as oq
@@ -255,3 +257,149 @@ def test_ipm_wave_vs_quad_kernel(dev, monkeypatch, N, ts, w, seed):
     assert np.abs(zw - zq).max() < TOL_F64
     its_w, its_q = (sw >> 8) & 0xFFFF, (sq >> 8) & 0xFFFF
     assert (np.abs(its_w - its_q) <= 1).mean() >= 0.9, (its_w, its_q)
+
+
+# ---------------------------------------------------------------------------
+# Every kernel mpcqp_mpc_ipm can choose, on the time-varying (4, 2) batch of
+# tests/_ipm_cases.py (N = 12, 16 instances, built on the CPU, solved there by
+# the oracle), and the exits of the iteration control.  The knobs are read at
+# every launch.
+KERNELS = {
+    "wave": {},                                             # ipm_wave_kernel
+    "quad1": {"MPCQP_IPM_WAVE": "0"},                       # ipm_quad_kernel<., 1>
+    "quad2": {"MPCQP_IPM_G": "2"},                          # ipm_quad_kernel<., 2>
+    "quad4": {"MPCQP_IPM_G": "4"},                          # ipm_quad_kernel<., 4>
+    "lane_lds": {"MPCQP_IPM_QUAD": "0"},                    # ipm_lds_kernel<., 4, 2, G>
+    "lane": {"MPCQP_IPM_QUAD": "0", "MPCQP_IPM_LDS": "0"},  # ipm_kernel<., 4, 2>
+}
+OUTPUTS = ("z", "y", "X", "lam_u", "pi", "status")
+
+
+def _tv_run(dev, monkeypatch, kernel, dt=torch.float64, x0=None, **kw):
+    for k, v in KERNELS[kernel].items():
+        monkeypatch.setenv(k, v)
+    b = ic.tv_batch()
+    t = lambda a: _t(np.array(a), dev, dt)  # noqa: E731 (a copy: the shared batch is read-only)
+    r = batched.mpc_ipm(t(b["A"]), t(b["B"]), t(ic.Q), t(ic.R), t(ic.QF), ic.N,
+                        t(b["x0"] if x0 is None else x0), xlo=t(-ic.XHI), xhi=t(ic.XHI),
+                        lb=t(np.tile(-ic.UHI, ic.N)), ub=t(np.tile(ic.UHI, ic.N)), c=t(b["c"]),
+                        tv=True, **kw)
+    torch.cuda.synchronize()
+    for k in KERNELS[kernel]:
+        monkeypatch.delenv(k)
+    return {k: r[k].cpu().numpy() for k in OUTPUTS}
+
+
+def _check_tv(r, o, b, tol_z, tol_y):
+    """Optimal and polished; z, X, y against the oracle; lam_u with the
+    condensed QP's stationarity and pi with the stage-wise one."""
+    st = r["status"]
+    assert ((st & 0xFF) == 0).all(), st & 0xFF
+    assert ((st & STATUS_POLISHED) != 0).all()
+    Z, Y, X = r["z"].astype(float), r["y"].astype(float), r["X"].astype(float)
+    X = X.reshape(ic.BATCH, -1)
+    ez = float(np.abs(Z - o["z"]).max())
+    ex = float(np.abs(X - o["X"]).max())
+    ey = float((np.abs(Y - o["y"]).max(1) / (1.0 + np.abs(o["y"]).max(1))).max())
+    print("z", ez, "X", ex, "y", ey)
+    assert ez < tol_z, ez
+    assert ex < tol_z, ex
+    assert ey < tol_y, ey
+    if tol_z > TOL_F64:
+        return
+    LU, PI = r["lam_u"], r["pi"]
+    for i in range(ic.BATCH):
+        d = o["d"][i]
+        scale = 1e-8 * (1 + np.abs(d["f"]).max())
+        g = d["H"] @ Z[i] + d["f"] + d["Gam"].T @ Y[i] + LU[i]
+        assert np.abs(g).max() < scale
+        x, u, y = X[i].reshape(ic.N, ic.NX), Z[i].reshape(ic.N, ic.NU), Y[i].reshape(ic.N, ic.NX)
+        for k in range(ic.N):  # pi_{k+1}: the costate of x_{k+1} = A_k x_k + B_k u_k + c_k
+            last = k == ic.N - 1
+            gx = (ic.QF if last else ic.Q) @ x[k] + y[k] - PI[i, k]
+            if not last:
+                gx = gx + b["A"][i, k + 1].T @ PI[i, k + 1]
+            gu = ic.R @ u[k] + b["B"][i, k].T @ PI[i, k] + LU[i].reshape(ic.N, ic.NU)[k]
+            assert max(np.abs(gx).max(), np.abs(gu).max()) < scale
+
+
+@pytest.mark.parametrize("kernel", list(KERNELS))
+def test_ipm_tv_batch_every_kernel(dev, monkeypatch, kernel):
+    _check_tv(_tv_run(dev, monkeypatch, kernel), ic.tv_oracle(), ic.tv_batch(), TOL_F64, 1e-7)
+
+
+def test_ipm_tv_batch_f32_storage(dev, monkeypatch):
+    """fp32 storage, fp64 arithmetic: against the oracle on the fp32-rounded
+    inputs, with the bound of test_ipm_f32_inputs."""
+    rd = lambda a: np.asarray(a, np.float32).astype(float)  # noqa: E731
+    b = {k: rd(v) for k, v in ic.tv_batch().items()}
+    o = ic.solve_oracle(Q=rd(ic.Q), R=rd(ic.R), QF=rd(ic.QF), **b)
+    _check_tv(_tv_run(dev, monkeypatch, "wave", torch.float32), o, b, 1e-6, 1e-6)
+
+
+def test_ipm_lane_kernels_agree_bitwise(dev, monkeypatch):
+    """ipm_lds_kernel and ipm_kernel run the same lane routine."""
+    r1, r2 = _tv_run(dev, monkeypatch, "lane_lds"), _tv_run(dev, monkeypatch, "lane")
+    for k in OUTPUTS:
+        assert r1[k].tobytes() == r2[k].tobytes(), k
+
+
+def test_ipm_cfg2_golden_global_workspace(dev, golden, monkeypatch):
+    """ipm_kernel<., 2, 1> (MPCQP_IPM_LDS=0) on the config-2 golden."""
+    monkeypatch.setenv("MPCQP_IPM_LDS", "0")
+    g = golden("boxqp_cfg2.npz")
+    t = lambda a: _t(a, dev)  # noqa: E731
+    r = batched.mpc_ipm(t(g["A"]), t(g["B"]), t(g["Q"]), t(g["R"]), t(g["Pf"]), int(g["N"]),
+                        t(g["x0"]), lb=-1.0, ub=1.0)
+    torch.cuda.synchronize()
+    st = r["status"].cpu().numpy()
+    assert ((st & 0xFF) == 0).all() and ((st & STATUS_POLISHED) != 0).all()
+    err = float(np.abs(r["z"].cpu().numpy() - g["z"]).max())
+    assert err < TOL_F64, err
+
+
+LADDER_KERNELS = ["wave", "quad1", "lane_lds"]
+
+
+@pytest.mark.parametrize("kernel", LADDER_KERNELS + ["lane"])
+def test_ipm_ladder_maxiter(dev, monkeypatch, kernel):
+    st = _tv_run(dev, monkeypatch, kernel, max_iter=2)["status"]
+    assert ((st & 0xFF) == STATUS_MAXITER).all(), st
+    assert (((st >> 8) & 0xFFFF) == 2).all()
+    assert ((st & STATUS_POLISHED) == 0).all()
+
+
+@pytest.mark.parametrize("kernel", LADDER_KERNELS)
+def test_ipm_ladder_strict_not_convex(dev, monkeypatch, kernel):
+    st = _tv_run(dev, monkeypatch, kernel, strict=True,
+                 H2=_t(ic.h2_nonconvex(), dev))["status"]
+    assert ((st & 0xFF) == STATUS_NOT_CONVEX).all(), st
+    if kernel == "lane_lds":
+        assert (((st >> 8) & 0xFFFF) == ic.STRICT).all()
+
+
+@pytest.mark.parametrize("kernel", LADDER_KERNELS)
+def test_ipm_ladder_nonfinite_and_skip(dev, monkeypatch, kernel):
+    """A NaN instance ends NONFINITE and leaves its neighbours' outputs as in
+    the run without it; skipped instances keep their pre-filled outputs."""
+    ref = _tv_run(dev, monkeypatch, kernel)
+    r = _tv_run(dev, monkeypatch, kernel, x0=ic.x0_nan(ic.tv_batch()["x0"]))
+    assert (r["status"][1] & 0xFF) == STATUS_NONFINITE
+    others = np.arange(ic.BATCH) != 1
+    for k in OUTPUTS:
+        assert r[k][others].tobytes() == ref[k][others].tobytes(), k
+    skip = torch.zeros(ic.BATCH, dtype=torch.int32, device=dev)
+    skip[::3] = 4
+    skip[1] = 2  # not in the mask: solved
+    shapes = dict(z=(ic.N * ic.NU,), y=(ic.N * ic.NX,), lam_u=(ic.N * ic.NU,),
+                  X=(ic.N, ic.NX), pi=(ic.N, ic.NX))
+    out = {k: torch.full((ic.BATCH,) + s, -7.5, dtype=torch.float64, device=dev)
+           for k, s in shapes.items()}
+    out["status"] = torch.full((ic.BATCH,), 77, dtype=torch.int32, device=dev)
+    r = _tv_run(dev, monkeypatch, kernel, skip=skip, skip_mask=4, out=out)
+    sk = (skip.cpu().numpy() & 4) != 0
+    assert (r["status"][sk] == 77).all()
+    for k in shapes:
+        assert (r[k][sk] == -7.5).all(), k
+        assert r[k][~sk].tobytes() == ref[k][~sk].tobytes(), k
+    assert (r["status"][~sk] == ref["status"][~sk]).all()

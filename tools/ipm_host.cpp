@@ -1,9 +1,12 @@
 // ipm_host.cpp -- DEVELOPMENT TOOL ONLY: the lane routine of ipm.hip
 // (ipm_lane.hpp) compiled for the host CPU, so the interior-point algorithm
 // can be stepped through and compared with the oracle without a GPU.  It is
-// not part of libmpcqp.so and nothing in the package, tests or bench loads it.
+// not part of libmpcqp.so; tests/test_ipm_host.py compiles and loads it (the
+// STRICT environment knob, read at every call, is part of that test's
+// contract; MUP is for experiments).
 //   g++ -O2 -shared -fPIC -I include tools/ipm_host.cpp -o /tmp/libipm_host.so
 #define MPCQP_HD
+#include <cstdio>
 #include <cstdlib>
 #include <vector>
 
