@@ -18,6 +18,8 @@
  *                       reports lam_p = dJ/dx0 only): dL/d(H, f, lb, ub) from dL/dz.
  *                       mpcqp_mpc_box_loop_vjp is the same through a whole
  *                       closed-loop episode (simulate(...), main.py:270-271).
+ *                       mpcqp_diff.h carries them on to the model: the adjoint
+ *                       of condensing, dL/d(H, F, f) -> dL/d(A, B, c, Q, R, Qf, x0).
  *   mpcqp_mpc_box    <- both of the above fused for the input-box OCP
  *                       (MPCController.solve end to end, one launch).
  *   mpcqp_mpc_qp     <- MPCController.solve end to end with the input box AND
@@ -716,9 +718,11 @@ int mpcqp_mpc_box_loop_affine(int dtype, int batch, int nx, int nu, int N, int s
  * step ahead.  No scratch; the call only enqueues on `stream` and allocates
  * nothing.  Limits: nx <= 4, nu <= 2, N*nu <= 32 (MPCQP_EINVAL outside, as
  * mpcqp_mpc_box_loop); batch == 0 returns MPCQP_OK.
- * Not supported: gradients through the condensing recursion (A, B -> H, F:
- * gA and gB are those of the simulated plant only), the polytope, soft and
- * bicycle loops, second derivatives, sweeps carried from one step to the next.
+ * gA and gB are those of the simulated plant only: the gradients through the
+ * condensing recursion (A, B -> H, F) are what mpcqp_condense_vjp of
+ * mpcqp_diff.h makes of gH and gF.
+ * Not supported: the polytope, soft and bicycle loops, second derivatives,
+ * sweeps carried from one step to the next.
  */
 int mpcqp_mpc_box_loop_vjp(int dtype, int batch, int nx, int nu, int N, int steps,
                            const void* H, int64_t strideH, const void* F, int64_t strideF,

@@ -22,19 +22,29 @@ Submodules:
   autograd       solve_box_diff, mpc_box_diff: the box QP and the fused box-MPC
                  step as torch.autograd functions; box_loop_diff,
                  mpc_box_loop_diff: the one-launch box-MPC episode with a
-                 one-launch backward (all four also exported here)
+                 one-launch backward; condense_diff, mpc_box_model_diff,
+                 mpc_box_loop_model_diff: the same with gradients of the
+                 prediction model A, B, c (all seven also exported here)
+  condense_diff  condense_vjp: the adjoint of condensing on the device
 """
 from . import _native  # noqa: F401
 
 __version__ = "0.1.0"
 
-_AUTOGRAD = ("solve_box_diff", "mpc_box_diff", "box_loop_diff", "mpc_box_loop_diff")
+_AUTOGRAD = ("solve_box_diff", "mpc_box_diff", "box_loop_diff", "mpc_box_loop_diff",
+             "condense_diff", "mpc_box_model_diff", "mpc_box_loop_model_diff")
 __all__ = ["library_path", *_AUTOGRAD]
 
 
 def __getattr__(name):
     # the autograd entry points, resolved on first use so that importing
     # the package stays free of torch
+    if name == "condense_diff":
+        # also the name of a submodule: the module itself, which is callable
+        # as autograd.condense_diff, so the name is one object either way
+        import importlib
+
+        return importlib.import_module(".condense_diff", __name__)
     if name in _AUTOGRAD:
         from . import autograd
 

@@ -99,6 +99,14 @@ _TABLE = {
 SIGNATURES = {name: (_KINDS[s[0]], [_KINDS[c] for c in s[1:].replace(" ", "")])
               for name, s in _TABLE.items()}
 
+# The symbols of include/mpcqp_diff.h, in the same notation
+# (tests/test_condense_vjp_host.py checks them against that header).
+_TABLE_DIFF = {
+    "mpcqp_condense_vjp": "i iiiiii pl pl pl pl pl pl pl ppp ppppppp p p",
+}
+SIGNATURES_DIFF = {name: (_KINDS[s[0]], [_KINDS[c] for c in s[1:].replace(" ", "")])
+                   for name, s in _TABLE_DIFF.items()}
+
 ABI_VERSION = 1
 
 _lock = threading.Lock()
@@ -122,7 +130,7 @@ def load(path: str | None = None):
                 "`python -c 'import __graft_entry__ as g; g.build()'` "
                 "(the HIP path has no CPU fallback)")
         lib = ctypes.CDLL(p)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_DIFF.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -27,6 +27,12 @@ backward one launch of ``batched.mpc_box_loop_vjp`` (include/mpcqp.h
 
 with the same conventions; an instance with a step that did not end OPTIMAL
 contributes exact zeros.  nx <= 4, nu <= 2, n <= 32.
+
+``condense_diff``, ``mpc_box_model_diff`` and ``mpc_box_loop_model_diff`` carry
+the graph on to the prediction model: their backward passes end in one launch
+of ``condense_diff.condense_vjp`` (include/mpcqp_diff.h ``mpcqp_condense_vjp``),
+the adjoint of the condensing recursion, which maps dL/dH, dL/dF and dL/df to
+A, B, c, Q, R, Qf and x0.  Same limits.
 """
 from __future__ import annotations
 
@@ -34,8 +40,10 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import batched
+from . import condense_diff as _cdiff
 
-__all__ = ["solve_box_diff", "mpc_box_diff", "box_loop_diff", "mpc_box_loop_diff"]
+__all__ = ["solve_box_diff", "mpc_box_diff", "box_loop_diff", "mpc_box_loop_diff",
+           "condense_diff", "mpc_box_model_diff", "mpc_box_loop_model_diff"]
 
 MAX_N = batched.BOX_VJP_MAX_N
 
@@ -289,4 +297,155 @@ def mpc_box_loop_diff(A, B, Q, R, Qf, N, x0, lb=None, ub=None, *, steps, x_ref=N
             Gam = Gam[0]
         g = batched.tracking_terms({"Gam": Gam}, Q, R, Qf, N, T, x_ref, u_ref)
     return box_loop_diff(H, F, A, B, x0, lb, ub, steps=T, g=g, w=w, cold=cold, max_iter=max_iter,
+                         tol=tol)
+
+
+# ------------------------------------------------ gradients of the model
+_COND_DIFF = ("H", "F", "f")  # the outputs of condensing that mpcqp_condense_vjp takes back
+
+
+def _r_matrix(R, nu: int):
+    """R as a matrix, by torch operations that carry its graph: a 0-dim R is
+    R I (its gradient is the trace of the matrix's), a vector the diagonal."""
+    if R.ndim == 0:
+        return R * torch.eye(nu, dtype=R.dtype, device=R.device)
+    if R.ndim == 1:
+        if R.shape[0] != nu:
+            raise ValueError(f"R of shape {tuple(R.shape)} with nu={nu}")
+        return torch.diag(R)
+    return R
+
+
+def _model_limits(who: str, nx: int, nu: int, n: int):
+    if nx > _cdiff.MAX_NX or nu > _cdiff.MAX_NU or n > _cdiff.MAX_N:
+        raise NotImplementedError(
+            f"{who}: gradients are limited to nx <= {_cdiff.MAX_NX}, nu <= {_cdiff.MAX_NU}, "
+            f"N * nu <= {_cdiff.MAX_N}, got nx = {nx}, nu = {nu}, N * nu = {n}")
+
+
+def _plant_tensors(A, B, Q, R, Qf):
+    """A, B, Q, R (a matrix), Qf as tensors of A's dtype on its device."""
+    dt, dev = A.dtype, A.device
+    A, B, Q, R, Qf = (torch.as_tensor(v, dtype=dt, device=dev) for v in (A, B, Q, R, Qf))
+    return A, B, Q, _r_matrix(R, int(B.shape[-1])), Qf
+
+
+class _Condense(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, A, B, Q, R, Qf, x0, c, N, tv, outputs):
+        cd = batched.condense(A, B, Q, R, Qf, N, x0=x0, c=c, tv=tv, outputs=outputs)
+        out = tuple(cd[k] for k in outputs)
+        ctx.mark_non_differentiable(*(v for k, v in zip(outputs, out) if k not in _COND_DIFF))
+        ctx.set_materialize_grads(False)
+        _stash(ctx, (A, B, Q, R, Qf), (x0, c))
+        ctx.N, ctx.tv, ctx.outputs = N, tv, outputs
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *gs):
+        A, B, Q, R, Qf, x0, c = _recover(ctx, 5)
+        names = ("gA", "gB", "gQ", "gR", "gQf", "gx0", "gc")
+        want = tuple(k for k, nd in zip(names, ctx.needs_input_grad) if nd)
+        up = {k: None if g is None else g.to(A.dtype) for k, g in zip(ctx.outputs, gs)}
+        r = _cdiff.condense_vjp(A, B, Q, R, Qf, ctx.N, x0, c, tv=ctx.tv, gH=up.get("H"),
+                                gF=up.get("F"), gf=up.get("f"), need=want)
+        return (*(r[k] for k in names), None, None, None)
+
+
+def condense_diff(A, B, Q, R, Qf, N, x0=None, c=None, *, tv=False, outputs=("H", "F", "f")):
+    """``batched.condense`` with gradients: returns the requested ``outputs``
+    (among H (packed), F, f), in that order, bit for bit those of
+    ``batched.condense``, carrying the graph to A, B, Q, R, Qf, c and x0.  The
+    backward pass is one launch of ``condense_diff.condense_vjp``; the gradient
+    of a shared input is summed over the batch, those of Q, R, Qf are symmetric.
+    R may be a matrix, a 0-dim tensor (R I: its gradient is the trace) or a
+    vector (the diagonal).  nx <= 4, nu <= 2, N * nu <= 32."""
+    outputs = tuple(outputs)
+    if set(outputs) - set(_COND_DIFF):
+        raise ValueError(f"condense_diff: outputs are among {_COND_DIFF}, got {outputs}")
+    A, B, Q, R, Qf = _plant_tensors(A, B, Q, R, Qf)
+    if _needs(A, B, Q, R, Qf, x0, c):
+        _model_limits("condense_diff", int(B.shape[-2]), int(B.shape[-1]), int(N) * int(B.shape[-1]))
+    return _Condense.apply(A, B, Q, R, Qf, x0, c, int(N), bool(tv), outputs)
+
+
+class _MpcBoxModel(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, A, B, Q, R, Qf, x0, lb, ub, c, N, tv, kw):
+        z, status = batched.mpc_box(A, B, Q, R, Qf, N, x0, lb, ub, c, tv=tv, **kw)
+        ctx.mark_non_differentiable(status)
+        _stash(ctx, (A, B, Q, R, Qf, x0, z, status), (lb, ub, c))
+        ctx.N, ctx.tv = N, tv
+        return z, status
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gz, _gstatus):
+        A, B, Q, R, Qf, x0, z, status, lb, ub, c = _recover(ctx, 8)
+        need = ctx.needs_input_grad  # A, B, Q, R, Qf, x0, lb, ub, c
+        batch = z.shape[0]
+        H = batched.condense(A, B, Q, R, Qf, ctx.N, x0=x0, c=c, tv=ctx.tv, outputs=("H",))["H"]
+        # dL/dH per instance, also where one H serves the batch: the instances'
+        # x0 differ, and with them what condense_vjp makes of gf
+        r = batched.solve_box_vjp(H.expand(batch, -1), z, lb, ub, gz.to(z.dtype), status=status,
+                                  need_H=True)
+        names = ("gA", "gB", "gQ", "gR", "gQf", "gx0", None, None, "gc")
+        want = tuple(k for k, nd in zip(names, need) if nd and k)
+        g = _cdiff.condense_vjp(A, B, Q, R, Qf, ctx.N, x0, c, tv=ctx.tv, gH=r["gH"], gf=r["gf"],
+                                need=want) if want else {}
+        glb, gub = _bound_grad(r["glb"], lb, need[6]), _bound_grad(r["gub"], ub, need[7])
+        return (*(g.get(k) for k in names[:6]), glb, gub, g.get("gc"), None, None, None)
+
+
+def mpc_box_model_diff(A, B, Q, R, Qf, N, x0, lb=None, ub=None, c=None, *, tv=False, **kw):
+    """``batched.mpc_box`` (the fused condense + box-QP kernel) with gradients
+    of the model as well: returns ``(z, status)``, bit for bit those of
+    ``mpc_box``, where z carries the graph to A, B, c, Q, R, Qf, x0 and tensor
+    lb / ub.  The backward pass condenses the instances (``batched.condense``),
+    runs the box adjoint for d = dL/df, nu and dL/dH = d z'
+    (``batched.solve_box_vjp``), and one launch of ``condense_vjp(gH, gf=d)``
+    maps those to the inputs.  Conventions of ``mpc_box_diff`` and
+    ``condense_diff``.  nx <= 4, nu <= 2, N * nu <= 32."""
+    A, B, Q, R, Qf = _plant_tensors(A, B, Q, R, Qf)
+    if _needs(A, B, Q, R, Qf, x0, lb, ub, c):
+        _model_limits("mpc_box_model_diff", int(B.shape[-2]), int(B.shape[-1]),
+                      int(N) * int(B.shape[-1]))
+    return _MpcBoxModel.apply(A, B, Q, R, Qf, x0, lb, ub, c, int(N), bool(tv), kw)
+
+
+def mpc_box_loop_model_diff(A, B, Q, R, Qf, N, x0, lb=None, ub=None, *, steps, plant=None, w=None,
+                            x_ref=None, u_ref=None, cold=False, max_iter=0, tol=0.0):
+    """``batched.mpc_box_loop`` (the one-launch input-box MPC episode) with
+    gradients of the prediction model: returns ``(xs, us, zs, status)``, bit for
+    bit the values of ``mpc_box_loop(..., plans=True)``.  H and F come from
+    ``condense_diff`` on the model (A, B) and carry the graph to A, B, Q, R, Qf;
+    the episode is ``box_loop_diff`` on the simulated plant, ``plant = (Ap, Bp)``,
+    or on (A, B) itself when ``plant`` is None -- the gradient of A (and B) is then
+    the sum of the model's part, through H and F, and the simulated plant's.
+    Gradients also reach x0, tensor lb / ub, w and u_ref.  ``x_ref`` enters the
+    linear term through Gam, whose gradient ``condense_vjp`` does not take:
+    with it this raises NotImplementedError (``mpc_box_loop_diff`` tracks a state
+    reference with a detached model).  nx <= 4, nu <= 2, N * nu <= 32."""
+    if x_ref is not None:
+        raise NotImplementedError(
+            "mpc_box_loop_model_diff: x_ref together with gradients of the model is not "
+            "implemented (its linear term runs through Gam); use mpc_box_loop_diff with A and B "
+            "detached")
+    A, B, Q, R, Qf = _plant_tensors(A, B, Q, R, Qf)
+    N, T = int(N), int(steps)
+    nx, nu = int(B.shape[-2]), int(B.shape[-1])
+    _model_limits("mpc_box_loop_model_diff", nx, nu, N * nu)
+    g = None
+    if u_ref is None:
+        H, F = _Condense.apply(A, B, Q, R, Qf, None, None, N, False, ("H", "F"))
+    else:
+        # the condensing call of mpc_box_loop with a reference: Gam comes along
+        H, F, Gam = _Condense.apply(A, B, Q, R, Qf, None, None, N, False, ("H", "F", "Gam"))
+        if Gam.shape[0] == 1:
+            Gam = Gam[0]
+        Rs = R.detach() + (_sym(R) - _sym(R).detach()) if _needs(R) else R
+        g = batched.tracking_terms({"Gam": Gam}, Q.detach(), Rs, Qf.detach(), N, T, None, u_ref)
+    Ap, Bp = (A, B) if plant is None else plant
+    return box_loop_diff(H, F, Ap, Bp, x0, lb, ub, steps=T, g=g, w=w, cold=cold, max_iter=max_iter,
                          tol=tol)
