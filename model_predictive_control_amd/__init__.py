@@ -24,15 +24,19 @@ Submodules:
                  mpc_box_loop_diff: the one-launch box-MPC episode with a
                  one-launch backward; condense_diff, mpc_box_model_diff,
                  mpc_box_loop_model_diff: the same with gradients of the
-                 prediction model A, B, c (all seven also exported here)
+                 prediction model A, B, c; poly_solve_diff, mpc_poly_diff: the
+                 polytope QP and the state-constrained MPC step (all nine also
+                 exported here)
   condense_diff  condense_vjp: the adjoint of condensing on the device
+  poly_diff      poly_solve_vjp, shared_grads: the adjoint of the polytope QP
 """
 from . import _native  # noqa: F401
 
 __version__ = "0.1.0"
 
 _AUTOGRAD = ("solve_box_diff", "mpc_box_diff", "box_loop_diff", "mpc_box_loop_diff",
-             "condense_diff", "mpc_box_model_diff", "mpc_box_loop_model_diff")
+             "condense_diff", "mpc_box_model_diff", "mpc_box_loop_model_diff",
+             "poly_solve_diff", "mpc_poly_diff")
 __all__ = ["library_path", *_AUTOGRAD]
 
 

@@ -107,6 +107,15 @@ _TABLE_DIFF = {
 SIGNATURES_DIFF = {name: (_KINDS[s[0]], [_KINDS[c] for c in s[1:].replace(" ", "")])
                    for name, s in _TABLE_DIFF.items()}
 
+# The symbols of include/mpcqp_poly_diff.h (tests/test_poly_vjp_host.py checks
+# them against that header).
+_TABLE_POLY_DIFF = {
+    "mpcqp_poly_solve_vjp_workspace": "z iiiii",
+    "mpcqp_poly_solve_vjp": "i iiiiii ppp pp pppp p pz p",
+}
+SIGNATURES_POLY_DIFF = {name: (_KINDS[s[0]], [_KINDS[c] for c in s[1:].replace(" ", "")])
+                        for name, s in _TABLE_POLY_DIFF.items()}
+
 ABI_VERSION = 1
 
 _lock = threading.Lock()
@@ -130,7 +139,8 @@ def load(path: str | None = None):
                 "`python -c 'import __graft_entry__ as g; g.build()'` "
                 "(the HIP path has no CPU fallback)")
         lib = ctypes.CDLL(p)
-        for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_DIFF.items()):
+        for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_DIFF.items(),
+                                  *SIGNATURES_POLY_DIFF.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -33,6 +33,18 @@ the graph on to the prediction model: their backward passes end in one launch
 of ``condense_diff.condense_vjp`` (include/mpcqp_diff.h ``mpcqp_condense_vjp``),
 the adjoint of the condensing recursion, which maps dL/dH, dL/dF and dL/df to
 A, B, c, Q, R, Qf and x0.  Same limits.
+
+``poly_solve_diff`` and ``mpc_poly_diff`` are the state-constrained half: the
+forward is ``batched.PolyQP.solve`` unchanged, the backward the adjoint of
+``poly_diff.poly_solve_vjp`` (include/mpcqp_poly_diff.h ``mpcqp_poly_solve_vjp``).
+With the active rows A = {i : y_i != 0} of C = [G; I], gz = dL/dz and gy = dL/dy:
+
+    e_A = M_AA^-1 (C Hinv gz - gy)_A,  dL/df = -Hinv (gz - C_A' e_A),
+    dL/dx0 = F' dL/df,  dL/dhl, dL/dhu = e on the side held,
+    dL/dH = dL/df z',  dL/dF = dL/df x0',  dL/dG = y dL/df' - e z'
+
+A row at its bound with a zero multiplier counts as inactive (the one-sided
+derivative on the side that lets it leave).  m_total <= 64, nx <= 16.
 """
 from __future__ import annotations
 
@@ -41,9 +53,11 @@ from torch.autograd.function import once_differentiable
 
 from . import batched
 from . import condense_diff as _cdiff
+from . import poly_diff as _pdiff
 
 __all__ = ["solve_box_diff", "mpc_box_diff", "box_loop_diff", "mpc_box_loop_diff",
-           "condense_diff", "mpc_box_model_diff", "mpc_box_loop_model_diff"]
+           "condense_diff", "mpc_box_model_diff", "mpc_box_loop_model_diff",
+           "poly_solve_diff", "mpc_poly_diff"]
 
 MAX_N = batched.BOX_VJP_MAX_N
 
@@ -449,3 +463,121 @@ def mpc_box_loop_model_diff(A, B, Q, R, Qf, N, x0, lb=None, ub=None, *, steps, p
     Ap, Bp = (A, B) if plant is None else plant
     return box_loop_diff(H, F, Ap, Bp, x0, lb, ub, steps=T, g=g, w=w, cold=cold, max_iter=max_iter,
                          tol=tol)
+
+
+# ------------------------------------------------ the polytope QP
+def _batch_grad(g, ref):
+    """The per-instance gradient ``g`` (b, w) for the operand ``ref``: summed
+    over the batch where ``ref`` is shared ((w,))."""
+    return g if ref.ndim == 2 else g.sum(0)
+
+
+class _PolySolve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, H, G, F, x0, f, hl, hu, lbz, ubz, qp, kw):
+        if qp is None:
+            qp = batched.PolyQP(H, G, F, lbz, ubz)
+        z, y, status = qp.solve(x0, f, hl, hu, **kw)
+        ctx.mark_non_differentiable(status)
+        ctx.set_materialize_grads(False)
+        _stash(ctx, (z, y, status), (x0, f, hl, hu, lbz, ubz))
+        ctx.qp = qp
+        return z, y, status
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gz, gy, _gstatus):
+        z, y, status, x0, f, hl, hu, lbz, ubz = _recover(ctx, 3)
+        qp = ctx.qp
+        need = ctx.needs_input_grad  # H, G, F, x0, f, hl, hu, lbz, ubz
+        m = qp.m
+        dt = z.dtype
+        want = ["gf", "ghl", "ghu"] + (["gx0"] if need[3] else [])
+        r = _pdiff.poly_solve_vjp(qp, y, None if gz is None else gz.to(dt),
+                                  None if gy is None else gy.to(dt), status=status, need=want)
+        names = ("gH", "gG", "gF", None, None, None, None, "glbz", "gubz")
+        shared = tuple(k for k, nd in zip(names, need) if k and nd)
+        s = _pdiff.shared_grads(qp, x0, z, y, r["gf"], r["e"], r["vstatus"],
+                                need=shared) if shared else {}
+        gH, gG, gF = (s.get(k) if nd else None for k, nd in zip(names[:3], need[:3]))
+        gx0 = _batch_grad(r["gx0"], x0) if need[3] else None
+        gf = _batch_grad(r["gf"], f) if need[4] else None
+        ghl = _batch_grad(r["ghl"][:, :m], hl) if need[5] else None
+        ghu = _batch_grad(r["ghu"][:, :m], hu) if need[6] else None
+        glbz = _bound_grad(s.get("glbz"), lbz, need[7])
+        gubz = _bound_grad(s.get("gubz"), ubz, need[8])
+        return gH, gG, gF, gx0, gf, ghl, ghu, glbz, gubz, None, None
+
+
+def poly_solve_diff(H, G, F, x0=None, f=None, hl=None, hu=None, lbz=None, ubz=None, *, qp=None,
+                    **kw):
+    """``batched.PolyQP(H, G, F, lbz, ubz).solve(x0, f, hl, hu)`` with
+    gradients: returns ``(z, y, status)``, bit for bit the values of
+    ``PolyQP.solve``, where z and y carry the graph to x0, f, hl, hu (per
+    instance, or shared: summed over the batch), tensor lbz / ubz
+    (Python-scalar bounds get none), packed H, G and F; status is
+    non-differentiable.  The backward pass is ``poly_diff.poly_solve_vjp`` and,
+    for the operands the batch shares, ``poly_diff.shared_grads``.  An instance
+    whose forward did not end OPTIMAL (or whose adjoint meets a NaN or
+    dependent active rows) contributes exact zeros to every gradient.
+    ``qp``: a ``PolyQP`` the caller built from the same H, G, F, lbz and ubz;
+    it skips the setup (the shared inverse and products) of every call, and the
+    gradients still go to the tensors passed here.  Keyword arguments
+    (max_iter, tol) go to ``solve``."""
+    return _PolySolve.apply(H, G, F, x0, f, hl, hu, lbz, ubz, qp, kw)
+
+
+def mpc_poly_diff(A, B, Q, R, Qf, N, x0, xlo=None, xhi=None, lb=None, ub=None, **kw):
+    """One step of the linear MPC with a state box on x_1..x_N and an input
+    box (the problem ``batched.mpc_poly_loop`` solves at every step), with
+    gradients: returns ``(z, y, status)`` of the condensed QP, where z (b, N*nu)
+    and y (b, rows) carry the graph to x0 (b, nx), xlo / xhi (scalar, (nx,) or
+    (N*nx,)), lb / ub (scalar, (nu,) or (N*nu,)) given as tensors, and to the
+    shared weights Q, R, Qf.  The shared model (A, B) is condensed once, as
+    ``mpc_poly_loop`` does (H, F, Gam, Phi); the rows are xlo - Phi x0 <= Gam z
+    <= xhi - Phi x0, taken as torch expressions, so that autograd carries their
+    part of dL/dx0, and ``poly_solve_diff`` does the rest.  The weights'
+    gradients come from one batch-1 call of ``condense_diff.condense_vjp`` on
+    dL/dH and dL/dF -- exact, since Gam and Phi do not depend on the weights --
+    within that adjoint's limits nx <= 4, nu <= 2, N * nu <= 32: outside them
+    weights that require grad raise NotImplementedError.  So do A or B that
+    require grad: their gradient needs dL/dGam and dL/dPhi, which
+    ``condense_vjp`` does not take."""
+    if _needs(A, B):
+        raise NotImplementedError(
+            "mpc_poly_diff: gradients through A and B need dL/dGam and dL/dPhi, which the "
+            "adjoint of condensing does not take; detach them")
+    N = int(N)
+    dt, dev = batched._dt_dev(A)
+    A, B = batched._dev(A, dt, dev), batched._dev(B, dt, dev)
+    if A.ndim != 2 or B.ndim != 2:
+        raise ValueError("mpc_poly_diff: the model (A, B) is shared by the batch")
+    nx, nu = int(B.shape[0]), int(B.shape[1])
+    outputs = ("H", "F", "Gam", "Phi")
+    if _needs(Q, R, Qf):
+        _model_limits("mpc_poly_diff", nx, nu, N * nu)
+        cd = _Condense.apply(*_plant_tensors(A, B, Q, R, Qf), None, None, N, False, outputs)
+    else:
+        cd = tuple(batched.condense(A, B, Q, R, Qf, N, outputs=outputs)[k] for k in outputs)
+    H, F, Gam, Phi = (v[0] for v in cd)
+
+    def stage_bound(v, width, name):
+        if v is None:
+            return None
+        t = torch.as_tensor(v, dtype=dt, device=dev)
+        if t.ndim == 0 or tuple(t.shape) == (width,):
+            return t.expand(width).repeat(N)
+        if tuple(t.shape) == (N * width,):
+            return t
+        raise ValueError(f"{name}: expected a scalar, ({width},) or ({N * width},), "
+                         f"got {tuple(t.shape)}")
+
+    x0 = torch.as_tensor(x0, dtype=dt, device=dev)
+    if x0.ndim != 2:
+        raise ValueError(f"mpc_poly_diff: x0 must be (batch, {nx}), got {tuple(x0.shape)}")
+    hl, hu = stage_bound(xlo, nx, "xlo"), stage_bound(xhi, nx, "xhi")
+    rows = hl is not None or hu is not None
+    free = x0 @ Phi.transpose(0, 1)
+    hl, hu = (None if h is None else h[None, :] - free for h in (hl, hu))
+    return poly_solve_diff(H, Gam if rows else None, F, x0, None, hl, hu,
+                           stage_bound(lb, nu, "lb"), stage_bound(ub, nu, "ub"), **kw)

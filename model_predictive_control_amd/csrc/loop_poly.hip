@@ -48,6 +48,7 @@
 // adds them.  AFFINE is a template flag like SOFT: the four
 // instantiations without it compile to what they were.
 #include "dual_range_core.hpp"
+#include "poly_prep.hpp"
 #include "poly_ws.hpp"
 
 // Steps between two rebuilds of W from M ("Poly loop").
@@ -665,6 +666,23 @@ __global__ __launch_bounds__(kPrepThreads) void poly_affine_prep_kernel(
   }
 }
 
+// The one launch site of poly_affine_prep_kernel (poly_prep.hpp).
+int launch_poly_affine_prep(const char* who, int dtype, const void* g, int64_t R, int n, int mt,
+                            const void* Hinv, const void* Ut, void* zg, void* sg,
+                            hipStream_t st) {
+  const int64_t blocks = (R + kPrepRows - 1) / kPrepRows;
+  MPCQP_CHECK_ARG(blocks <= 0x7fffffff, "%s: %lld rows of g exceed the grid", who, (long long)R);
+  auto run = [&](auto tp) {
+    using T = decltype(tp);
+    hipLaunchKernelGGL((poly_affine_prep_kernel<T>), dim3((unsigned)blocks), dim3(kPrepThreads),
+                       0, st, (const T*)g, R, n, mt, (const T*)Hinv, (const T*)Ut, (T*)zg,
+                       (T*)sg);
+    MPCQP_CHECK_LAUNCH("poly_affine_prep_kernel");
+    return (int)MPCQP_OK;
+  };
+  return dtype == MPCQP_F64 ? run(0.0) : run(0.0f);
+}
+
 // Scratch of mpcqp_mpc_poly_loop_affine: zg, then sg.
 struct PolyAffineWs {
   int64_t R, oZg, oSg, total;
@@ -765,13 +783,9 @@ static int poly_loop_entry(const char* who, int dtype, int batch, int n, int m, 
       if (g) {
         T* zg = (T*)((char*)scratch + S.oZg);
         T* sg = (T*)((char*)scratch + S.oSg);
-        const int64_t blocks = (S.R + kPrepRows - 1) / kPrepRows;
-        MPCQP_CHECK_ARG(blocks <= 0x7fffffff, "%s: %lld rows of g exceed the grid", who,
-                        (long long)S.R);
-        hipLaunchKernelGGL((poly_affine_prep_kernel<T>), dim3((unsigned)blocks),
-                           dim3(kPrepThreads), 0, st, (const T*)g, S.R, n, mt,
-                           (const T*)(base + L.oHinv), (const T*)(base + L.oUt), zg, sg);
-        MPCQP_CHECK_LAUNCH("poly_affine_prep_kernel");
+        const int rc = launch_poly_affine_prep(who, dtype, g, S.R, n, mt, base + L.oHinv,
+                                               base + L.oUt, zg, sg, st);
+        if (rc != MPCQP_OK) return rc;
         a.zg = zg; a.sg = sg;
       }
       return rho ? poly_loop_t<T, true, true>(a, st) : poly_loop_t<T, false, true>(a, st);

@@ -1,0 +1,128 @@
+"""The adjoint of the stand-alone polytope QP on the device
+(include/mpcqp_poly_diff.h ``mpcqp_poly_solve_vjp``), on torch tensors with the
+conventions of ``batched``.
+
+``poly_solve_vjp`` maps the gradients of a loss with respect to the outputs of
+``PolyQP.solve`` -- gz = dL/dz and gy = dL/dy -- to those of its per-instance
+operands: gf (the extra gradient f), gx0, and ghl / ghu over all m_total rows of
+[G; I], whose rows m.. are the instance's share of dL/dlbz and dL/dubz.
+``shared_grads`` forms the gradients of the operands the batch shares (H, F, G,
+lbz, ubz) from those, with torch products.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _native as nat
+from . import batched
+from .batched import _alloc, _ptr, _stream
+
+__all__ = ["poly_solve_vjp", "scratch_bytes", "shared_grads", "VJP_OUTPUTS"]
+
+VJP_OUTPUTS = ("gf", "gx0", "ghl", "ghu")
+
+
+def scratch_bytes(qp, batch: int) -> int:
+    """Bytes of the ``scratch=`` buffer of ``poly_solve_vjp`` for ``batch``
+    instances of ``qp`` (``mpcqp_poly_solve_vjp_workspace``)."""
+    return int(batched._lib().mpcqp_poly_solve_vjp_workspace(
+        batched._code(qp.dtype), int(batch), qp.n, qp.m, qp.nbox))
+
+
+def poly_solve_vjp(qp, y, gz=None, gy=None, *, status=None, need=VJP_OUTPUTS, scratch=None) -> dict:
+    """Adjoint of ``qp.solve`` (a ``batched.PolyQP``) at its optimum, two
+    launches.  ``y`` (b, m_total) and ``status`` (b,) are what ``solve``
+    returned (status None: every instance counts as OPTIMAL); ``gz`` (b, n) and
+    ``gy`` (b, m_total) are dL/dz and dL/dy, None meaning zero.  Returns a dict
+    with the entries of ``need`` (the others None) out of
+
+    * ``gf`` (b, n) = dL/df, ``gx0`` (b, nx) = dL/dx0 (only for a ``qp`` with F),
+      ``ghl``, ``ghu`` (b, m_total) = dL/dhl, dL/dhu on the rows below m and the
+      instance's dL/dlbz, dL/dubz on the rows from m on,
+
+    ``e`` = ghl + ghu when both were asked for (the adjoint's row variable, what
+    ``shared_grads`` takes) and ``vstatus`` (b,) int32: a bare STATUS_* code,
+    the forward's if that is not OPTIMAL, else NOT_CONVEX (H not positive
+    definite, or the rows marked active are dependent), NONFINITE, or OPTIMAL.
+    Every gradient of an instance whose vstatus is not OPTIMAL is exactly zero.
+    ``scratch``: a preallocated uint8 device buffer of ``scratch_bytes(qp, b)``
+    bytes (for graph capture); None allocates one when gz is given."""
+    dt, dev = qp.dtype, qp.ws.device
+    unknown = set(need) - set(VJP_OUTPUTS)
+    if unknown:
+        raise ValueError(f"need: unknown outputs {sorted(unknown)}")
+    if "gx0" in need and qp.nx == 0:
+        raise ValueError("gx0 asked for, but this PolyQP has no x0 -> gradient map F")
+    y = batched._dev(y, dt, dev)
+    if y.ndim != 2 or y.shape[1] != qp.mt:
+        raise ValueError(f"y must be (batch, {qp.mt}), got {tuple(y.shape)}")
+    batch = int(y.shape[0])
+    gz, gy = batched._dev(gz, dt, dev), batched._dev(gy, dt, dev)
+    for name, t, w in (("gz", gz, qp.n), ("gy", gy, qp.mt)):
+        if t is not None and tuple(t.shape) != (batch, w):
+            raise ValueError(f"{name} must be ({batch}, {w}), got {tuple(t.shape)}")
+    if status is not None and (status.dtype != torch.int32 or tuple(status.shape) != (batch,)
+                               or not status.is_contiguous()):
+        raise ValueError(f"status must be a contiguous int32 tensor of shape ({batch},)")
+    shapes = dict(gf=(batch, qp.n), gx0=(batch, qp.nx), ghl=(batch, qp.mt), ghu=(batch, qp.mt))
+    o = _alloc({**{k: (shapes[k], dt) if k in need else None for k in VJP_OUTPUTS},
+                "vstatus": ((batch,), torch.int32)}, dev, keyed=True)
+    nbytes = scratch_bytes(qp, batch) if gz is not None else 0
+    if scratch is None and nbytes:
+        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    elif scratch is not None and (scratch.device.type != "cuda"
+                                  or scratch.numel() * scratch.element_size() < nbytes):
+        raise ValueError(f"scratch must be a device buffer of >= {nbytes} bytes")
+    rc = batched._lib().mpcqp_poly_solve_vjp(
+        batched._code(dt), batch, qp.n, qp.m, qp.nbox, qp.nx, _ptr(qp.ws), _ptr(y), _ptr(status),
+        _ptr(gz), _ptr(gy), *(_ptr(o[k]) for k in VJP_OUTPUTS), _ptr(o["vstatus"]),
+        _ptr(scratch), 0 if scratch is None else scratch.numel() * scratch.element_size(),
+        _stream())
+    nat.check(rc, "mpcqp_poly_solve_vjp")
+    o["e"] = o["ghl"] + o["ghu"] if o["ghl"] is not None and o["ghu"] is not None else None
+    return o
+
+
+def shared_grads(qp, x0, z, y, gf, e, vstatus, need=("gH", "gF", "gG", "glbz", "gubz")) -> dict:
+    """The gradients of the operands of ``qp`` that the batch shares, from the
+    per-instance results of ``poly_solve_vjp`` (``gf``, ``e`` = ghl + ghu,
+    ``vstatus``) and the forward's ``x0`` (b, nx) or (nx,) or None, ``z`` and
+    ``y``.  With S = sum_b gf_b z_b':
+
+    * ``gH`` on the packed entries, folded as ``batched.solve_box_vjp`` does:
+      (i, j<i) = S_ij + S_ji, (i, i) = S_ii;
+    * ``gF`` (n, nx) = sum_b gf_b x0_b' (zeros without x0; None without F);
+    * ``gG`` (m, n) = the rows below m of sum_b (y_b gf_b' - e_b z_b') (None for m = 0);
+    * ``glbz``, ``gubz`` (n,) = the sums of e over the box rows held at their
+      lower / upper side (None without a box).
+
+    The rows of z, y (and x0) of every instance whose vstatus is not OPTIMAL are
+    zeroed first: the forward wrote NaN there, and 0 * NaN would poison the sums."""
+    ok = (vstatus == nat.STATUS_OPTIMAL)[:, None]
+    batch, n, m = int(z.shape[0]), qp.n, qp.m
+
+    def keep(t):
+        return torch.where(ok, t, torch.zeros_like(t))
+
+    z, y, gf, e = keep(z), keep(y), keep(gf), keep(e)
+    o = dict.fromkeys(("gH", "gF", "gG", "glbz", "gubz"))
+    if "gH" in need:
+        S = gf.transpose(0, 1) @ z
+        St = S + S.transpose(0, 1)
+        St = St - torch.diag(torch.diagonal(S))
+        o["gH"] = batched.pack_lower(St)
+    if "gF" in need and qp.nx > 0:
+        if x0 is None:
+            o["gF"] = torch.zeros((n, qp.nx), dtype=z.dtype, device=z.device)
+        else:
+            x0 = keep(x0.expand(batch, qp.nx))
+            o["gF"] = gf.transpose(0, 1) @ x0
+    if "gG" in need and m > 0:
+        o["gG"] = y[:, :m].transpose(0, 1) @ gf - e[:, :m].transpose(0, 1) @ z
+    if qp.nbox:
+        yb, eb = y[:, m:], e[:, m:]
+        if "glbz" in need:
+            o["glbz"] = torch.where(yb < 0, eb, torch.zeros_like(eb)).sum(0)
+        if "gubz" in need:
+            o["gubz"] = torch.where(yb > 0, eb, torch.zeros_like(eb)).sum(0)
+    return o
