@@ -201,13 +201,35 @@ struct QRowOwned<QSym<T, BS>> {
   static constexpr bool v = MPCQP_ROW_OWNER != 0;
 };
 
+// The trip of the active set on owned, keyed rows (gi_box_st): three pieces,
+// each with its own switch for A/B libraries (=0 builds the tree without it).
+//   MPCQP_FAST_TRIP    the ratio filter and the full-step trip
+//   MPCQP_BOUND_AHEAD  the next pivot's bounds and z_p are read a trip ahead
+//   MPCQP_SWEEP_RD     the sweep takes 1 / d from the trip's paths (the
+//                      full-step one holds it: rm); =0 forms it behind them.
+//                      Alone it does not pass the rule on the config-2 line;
+//                      it stays because without it the BS = 8 shapes are
+//                      slower than before the full-step trip.
+#ifndef MPCQP_FAST_TRIP
+#define MPCQP_FAST_TRIP 1
+#endif
+#ifndef MPCQP_BOUND_AHEAD
+#define MPCQP_BOUND_AHEAD 1
+#endif
+#ifndef MPCQP_SWEEP_RD
+#define MPCQP_SWEEP_RD 1
+#endif
+
 // KEY: keyed reductions where the layout has them (QKeyed); a kernel passes
 // false to keep one instantiation on the compare-and-select reductions.
-template <class Mat_, bool OWN_ROWS = QRowOwned<Mat_>::v, bool KEY = true>
+// TRIP: the three pieces above where the rows are owned and keyed; a kernel
+// passes false to keep one instantiation on the general trip alone.
+template <class Mat_, bool OWN_ROWS = QRowOwned<Mat_>::v, bool KEY = true, bool TRIP = true>
 struct RowOwn {  // replicated
   using Mat = Mat_;
   static constexpr bool OWNED = false;
   static constexpr bool KEYED = false;
+  static constexpr bool FAST = false, AHEAD = false, SWEEP_RD = false;
   static constexpr int BS = Mat::RPL;
   static constexpr int RO = BS;
   // slot s holds a row; its matrix row, to compare with a pivot (-1: none)
@@ -234,8 +256,8 @@ struct RowOwn {  // replicated
   }
 };
 
-template <class Mat_, bool KEY>
-struct RowOwn<Mat_, true, KEY> {  // owned (QSym)
+template <class Mat_, bool KEY, bool TRIP>
+struct RowOwn<Mat_, true, KEY, TRIP> {  // owned (QSym)
   using Mat = Mat_;
   static constexpr bool OWNED = true;
   static constexpr int BS = Mat::RPL;
@@ -276,6 +298,11 @@ struct RowOwn<Mat_, true, KEY> {  // owned (QSym)
   }
   // the same reduction on one key (QKeyed)
   static constexpr bool KEYED = KEY && QKeyed<Mat>::v;
+  // (=2: on the compare-and-select reductions of owned rows as well, fp32
+  // included; not the default)
+  static constexpr bool FAST = TRIP && (KEYED ? MPCQP_FAST_TRIP != 0 : MPCQP_FAST_TRIP == 2);
+  static constexpr bool AHEAD = TRIP && (KEYED ? MPCQP_BOUND_AHEAD != 0 : MPCQP_BOUND_AHEAD == 2);
+  static constexpr bool SWEEP_RD = FAST && MPCQP_SWEEP_RD != 0;
   using K = Key<key_bits(Mat::NMAX)>;
   template <bool MAX>
   static __device__ __forceinline__ void key_arg(double& key) {
@@ -314,6 +341,60 @@ __device__ __forceinline__ auto& own_or_full(A& own, B& full) {
 template <typename T>
 __device__ __forceinline__ T mu_rate(int st, T cs, T sgn) {
   return ((st == 1) ? -cs : ((st == 2) ? cs : T(0))) * sgn;
+}
+
+// The ratio filter: true when some row of this lane may block the step t2,
+// decided without the reciprocal of its multiplier rate.  It must be true
+// whenever ratio() below would return ti < t2; where no lane of a wave passes
+// it, the trip takes the full step without running the ratio test.
+//
+// The ratio test finds a candidate row (active, dmu < 0) blocking when
+// v(t) < t2 with t = fl(-mu * fast_rcp(dmu)) and v = Key::clear (keyed) or the
+// identity.  With a = -dmu > 0:
+//   fast_rcp      |r a + 1| <= 2^-51 (fp64, rcp + two Newton steps),
+//                 2^-22 (fp32, rcp + one);
+//   the product   one rounding, 2^-53 (2^-24);
+//   Key::clear    lowers a positive t by less than 2^(KB-52) <= 2^-47 relative
+//                 (KB <= 5) and never lowers a negative one;
+// so v(t) < t2 implies mu < t2 a (1 + e) with e < 2^-46 (fp64) or 2^-21 (fp32).
+// The filter compares mu with fl(fl(t2 (1 + DELTA)) a): two more roundings,
+// 2^-52 (2^-23) together.  DELTA = 2^-40 (fp64) and 2^-16 (fp32) leave a factor
+// of more than 30 over the sum.
+// The bounds are relative, so they hold only away from underflow: a product
+// below TINY passes the filter, and so does a step t2 outside [TINY, HUGE]
+// (ratio_range; HUGE = the sentinel of the reduction, which a larger t2 or a NaN
+// one would compare with).  A product that overflows is +inf and passes every
+// finite mu.  A NaN multiplier fails the comparison and an infinite one is no
+// smaller than any product: not blocking, as fmin(., big) / t < ti make them
+// in the ratio test.
+template <typename T>
+struct RatioFilter;
+template <>
+struct RatioFilter<double> {
+  static constexpr double DELTA = 0x1p-40, TINY = 0x1p-900;
+};
+template <>
+struct RatioFilter<float> {
+  static constexpr float DELTA = 0x1p-16f, TINY = 0x1p-100f;
+};
+// t2 (group-uniform) is in the range where the filter's bounds hold
+template <typename T>
+__device__ __forceinline__ bool ratio_range(T t2, T huge) {
+  return t2 >= RatioFilter<T>::TINY && t2 <= huge;
+}
+template <typename T, int RO>
+__device__ __forceinline__ bool ratio_filter(const int (&st)[RO], const T (&mu)[RO],
+                                             const T (&co)[RO], T rm, T sgn, T t2) {
+  const T t2d = t2 * (T(1) + RatioFilter<T>::DELTA);
+  bool f = false;
+#pragma unroll
+  for (int r = 0; r < RO; ++r) {
+    const T dmu = mu_rate(st[r], co[r] * rm, sgn);
+    const bool cand = (st[r] == 1 || st[r] == 2) && dmu < T(0);
+    const T rhs = t2d * -dmu;
+    f = f || (cand && (mu[r] < rhs || rhs < RatioFilter<T>::TINY));
+  }
+  return f;
 }
 
 // Compare-and-select on (value, index[, payload]).
@@ -368,6 +449,11 @@ struct SelCmp {
       k = take ? ri[r] : k;
     }
     Own::template arg<false>(ti, k);
+  }
+  // true whenever ratio() would give ti < t2 (RatioFilter); the sentinel is +inf
+  __device__ __forceinline__ bool may_block(const int (&st)[RO], const T (&mu)[RO],
+                                            const T (&co)[RO], T rm, T sgn, T t2) const {
+    return ratio_filter(st, mu, co, rm, sgn, t2) || !ratio_range(t2, Lim<T>::inf());
   }
   // z_p of a new pivot travels with the scan
   template <class Mat>
@@ -444,6 +530,12 @@ struct SelKey {
     Own::template key_arg<false>(key);
     ti = K::clear(key);
     k = K::code(key);
+  }
+  // true whenever ratio() would give ti < t2 (RatioFilter); the sentinel is big()
+  __device__ __forceinline__ bool may_block(const int (&st)[RO], const double (&mu)[RO],
+                                            const double (&co)[RO], double rm, double sgn,
+                                            double t2) const {
+    return ratio_filter(st, mu, co, rm, sgn, t2) || !ratio_range(t2, K::big());
   }
   // the owners publish their rows of z; a new pivot reads z_p from there
   __device__ __forceinline__ void publish(const Mat& M, const double (&zr)[RO]) const {
@@ -552,9 +644,11 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
     bool need_p = true;
     int p = 0, side = 1;
     T tgt = T(0), zp = T(0), gp = T(0);
-    // the scan of the trip before (below); a_zv stays unused on a key
+    // the scan of the trip before (below); a_zv stays unused on a key.  a_lb,
+    // a_ub, a_zp (AHEAD): the bounds and z of row a_pi, read behind that scan
     T a_viol = T(0), a_zv = T(0);
     int a_pi = 0;
+    [[maybe_unused]] T a_lb = T(0), a_ub = T(0), a_zp = T(0);
     bool have_scan = false;
     while (true) {
       if (__any(active && need_p)) {
@@ -572,10 +666,19 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
             active = false;  // settled (pending the exact re-check)
           } else {
             p = pi;
-            const T lbp = lbs[p], ubp = ubs[p];
-            zp = sel.pivot_z(p, zv);
-            side = (zp < lbp) ? 1 : 2;
-            tgt = (side == 1) ? lbp : ubp;
+            if constexpr (Own::AHEAD) {
+              // no LDS wait here but in the first trip of a pass, which has
+              // no scan-ahead and reads at the use
+              const T lbp = have_scan ? a_lb : lbs[p], ubp = have_scan ? a_ub : ubs[p];
+              zp = have_scan ? a_zp : sel.pivot_z(p, zv);
+              side = (zp < lbp) ? 1 : 2;
+              tgt = (side == 1) ? lbp : ubp;
+            } else {
+              const T lbp = lbs[p], ubp = ubs[p];
+              zp = sel.pivot_z(p, zv);
+              side = (zp < lbp) ? 1 : 2;
+              tgt = (side == 1) ? lbp : ubp;
+            }
             gp = T(0);
             need_p = false;
           }
@@ -594,63 +697,34 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
       const T rm = fast_rcp(mpp);
       const T sgn = (tgt > zp) ? T(1) : T(-1);
       const T t2 = fabs(tgt - zp);
-      T ti;
-      int k = 0;
-      sel.ratio(st, mu, co, rm, sgn, ti, k);
-      const bool partial = ti < t2;
-      const T s_eff = stepping ? (partial ? ti : t2) : T(0);
-#pragma unroll
-      for (int r = 0; r < RO; ++r) {
-        const T cs = co[r] * rm;  // dz per unit move of z_p (c stays raw for the sweep)
-        zr[r] = (st[r] == 0) ? fma(sgn * s_eff, cs, zr[r]) : zr[r];
-        mu[r] = fma(s_eff, mu_rate(st[r], cs, sgn), mu[r]);
-      }
-      gp = fma(-sgn * s_eff, rm, gp);  // d g_p / d z_p = -1 / M_pp
-      zp = fma(sgn, s_eff, zp);
-      MPCQP_PHASE(6);
-      // the index whose state changes: k joins F (partial) or p leaves it (full)
-      const int idx = partial ? k : p;
-      const T sigma = partial ? T(1) : T(-1);
-      // full steps sweep on p, whose column is still in registers: publish
-      // again only when some group of the wave drops a bound
-      T kr[BS], kcol[NC];
-      T d = mpp;
-      if (__any(stepping && partial)) {
-        d = M.column(idx, gb, kr, kcol);
+      // The rest of the trip, one body for two paths.  FULL: no group of the
+      // wave can take a partial step (the ratio filter, below), so partial is
+      // the constant false and with it idx = p, sigma = -1, the sweep column
+      // the pivot's; no ratio test, no second column publish.  Per group the
+      // arithmetic of a full step is that of the general path, in its order.
+      // The sweep itself follows the two paths (one copy: with one in each
+      // path M lived in two sets of registers, 169 -> 252 VGPRs at config 2)
+      // and takes from them the pivot idx, sigma, the column kr / kcol and
+      // d, or (SWEEP_RD) 1 / d, which the full-step path holds already.
+      [[maybe_unused]] T s_kr[BS], s_kcol[NC], s_sigma = T(-1), s_d = mpp;
+      [[maybe_unused]] int s_idx = p;
+      [[maybe_unused]] bool sweeping = false;
+      if constexpr (!Own::FAST) {
+#define MPCQP_TRIP_FULL false
+#include "gi_box_trip.inc"
+#undef MPCQP_TRIP_FULL
+      } else if (__any(stepping && sel.may_block(st, mu, co, rm, sgn, t2))) {
+#define MPCQP_TRIP_FULL false
+#include "gi_box_trip.inc"
+#undef MPCQP_TRIP_FULL
       } else {
-#pragma unroll
-        for (int r = 0; r < BS; ++r) kr[r] = c[r];
-#pragma unroll
-        for (int r = 0; r < NC; ++r) kcol[r] = cc[r];
+#define MPCQP_TRIP_FULL true
+#include "gi_box_trip.inc"
+#undef MPCQP_TRIP_FULL
       }
-      const bool bad = stepping && (partial ? !(d > T(0)) : !(d < T(0)));
-      // the state changes first, then the next pivot's scan: it reads only z
-      // and the states, so its arg-max chain runs ahead of (and can overlap)
-      // the sweep; used when the step was full (need_p)
-      if (stepping && !bad) {
-#pragma unroll
-        for (int r = 0; r < RO; ++r) {
-          const int i = ri[r];
-          if (partial && i == k) {
-            st[r] = 0;
-            mu[r] = T(0);
-          }
-          if (!partial && i == p) {
-            st[r] = side;
-            zr[r] = tgt;
-            mu[r] = (side == 1) ? gp : -gp;
-          }
-        }
-        need_p = !partial;
+      if constexpr (Own::FAST) {
+        if (sweeping) M.template sweep_col<Own::SWEEP_RD>(s_idx, s_sigma, s_d, s_kr, s_kcol);
       }
-      if (bad) {
-        code = MPCQP_STATUS_NOT_CONVEX;
-        active = false;
-      }
-      sel.publish(M, zr);
-      sel.scan(st, zr, B, a_viol, a_pi, a_zv);
-      have_scan = true;
-      if (stepping && !bad) M.sweep_col(idx, sigma, d, kr, kcol);
       MPCQP_PHASE(7);
     }
     // exact refresh for every group, then re-check the bounds

@@ -104,6 +104,18 @@ struct LoopKeyed {
   static constexpr bool v = !(sizeof(T) == 8 && NX == 4 && NU == 2 && BS == 5 && AFFINE);
 };
 
+// The full-step trip, the ratio filter and the bound read-ahead (RowOwn's TRIP,
+// gi_box_core.hpp) per instantiation; they exist on keyed rows only.
+// The fp64 BS = 2 kernels would spill under the 128 VGPRs of their four-wave
+// bound (120..124 VGPRs and no scratch -> 128 and 52..68 bytes per lane): they
+// keep the general trip alone.  No other kernel gains scratch or loses a wave
+// of its bound; fp64 BS = 5 (the config-2 loop) takes 13..23 AGPRs under its
+// one-wave bound (252 -> 273 + 17).
+template <typename T, int NX, int NU, int BS, bool AFFINE>
+struct LoopTrip {
+  static constexpr bool v = BS != 2;
+};
+
 // A wave-uniform pointer to global memory, held in scalar registers.
 template <typename T>
 using GlobalPtr = const __attribute__((address_space(1))) T*;
@@ -310,7 +322,8 @@ __global__ __launch_bounds__(64, (LoopOcc<T, BS>::w)) void box_loop_kernel(
     if (code == MPCQP_STATUS_OPTIMAL && !okp) code = MPCQP_STATUS_NOT_CONVEX;
     T zr[BS];
     int iters = 0;
-    using Own = RowOwn<QSym<T, BS>, QRowOwned<QSym<T, BS>>::v, LoopKeyed<T, NX, NU, BS, AFFINE>::v>;
+    using Own = RowOwn<QSym<T, BS>, QRowOwned<QSym<T, BS>>::v, LoopKeyed<T, NX, NU, BS, AFFINE>::v,
+                       LoopTrip<T, NX, NU, BS, AFFINE>::v>;
     const int c2 = gi_box_st<true, Own>(M, gb, fs, lbs, ubs, n, a.max_iter, a.tol,
                                         live && code == MPCQP_STATUS_OPTIMAL, zr, iters,
                                         st MPCQP_CLK_ARG);

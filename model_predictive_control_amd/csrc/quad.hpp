@@ -137,9 +137,14 @@ struct QSym {
   // sigma M_kj / d on row k, sigma M_ik / d on column k, -1/d at (k, k).
   // Row/column k are selected, not produced by cancellation (their relative
   // error would otherwise grow like eps * |d|).
+  // RD: d is already 1 / M_kk = fast_rcp(M_kk), from a caller that holds it (the
+  // full-step trip of gi_box_st).  One function with a flag and not a second
+  // one that the first forwards to: forwarding changes the instruction streams
+  // of five fp32 BS = 2 kernels that never pass RD.
+  template <bool RD = false>
   __device__ __forceinline__ void sweep_col(int k, T sigma, T d, const T (&colr)[BS],
                                             const T (&colc)[BS]) {
-    const T rd = fast_rcp(d);
+    const T rd = RD ? d : fast_rcp(d);
     T a[BS], scol[BS], srow[BS];
     bool ik[BS], jk[BS];
 #pragma unroll

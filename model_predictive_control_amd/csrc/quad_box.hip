@@ -174,6 +174,13 @@ struct QMpcKeyed {
   static constexpr bool v = !(sizeof(T) == 8 && NX == 4 && NU == 2 && Mat::RPL == 4);
 };
 
+// The full-step trip, the ratio filter and the bound read-ahead (RowOwn's TRIP,
+// gi_box_core.hpp) per instantiation; they exist on keyed rows only.
+template <typename T, int NX, int NU, class Mat>
+struct QMpcTrip {
+  static constexpr bool v = true;
+};
+
 template <typename T, int NX, int NU, class Mat>
 struct QMpcLds {
   static constexpr bool ROWS = QMpcRows<T, NX, NU, Mat::RPL>::v;
@@ -861,7 +868,8 @@ __global__ __launch_bounds__(64, OCC) void mpc_group_kernel(MpcArgsQ<T> a) {
   else if ((__ballot(badbox) & gmask) != 0) code = MPCQP_STATUS_INFEASIBLE;
   T zr[RPL];
   int iters = 0;
-  using Own = RowOwn<Mat, QMpcOwned<T, NX, NU, Mat>::v, QMpcKeyed<T, NX, NU, Mat>::v>;
+  using Own = RowOwn<Mat, QMpcOwned<T, NX, NU, Mat>::v, QMpcKeyed<T, NX, NU, Mat>::v,
+                     QMpcTrip<T, NX, NU, Mat>::v>;
   const int c2 = gi_box<Own>(M, gb, fs, lbs, ubs, n, a.max_iter, a.tol,
                              live && code == MPCQP_STATUS_OPTIMAL, zr, iters MPCQP_CLK_ARG);
   if (code == MPCQP_STATUS_OPTIMAL) code = c2;
