@@ -102,8 +102,9 @@ size_t mpcqp_poly_solve_vjp_workspace(int dtype, int batch, int n, int m, int nb
  *
  * Limits: those of mpcqp_poly_solve, m_total in [1, 64] and nx <= 16
  * (MPCQP_EINVAL outside them); batch == 0 returns MPCQP_OK.
- * Not supported: the adjoint of mpcqp_mpc_poly_loop and of its soft and affine
- * variants, mpcqp_solve_qp, second derivatives.
+ * Not supported: mpcqp_solve_qp, second derivatives.  (The adjoint of
+ * mpcqp_mpc_poly_loop and its affine variant is mpcqp_mpc_poly_loop_vjp of
+ * mpcqp_poly_loop_diff.h; the soft variant has none.)
  */
 int mpcqp_poly_solve_vjp(int dtype, int batch, int n, int m, int nbox, int nx,
                          const void* workspace, const void* y, const int32_t* status,

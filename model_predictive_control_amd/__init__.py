@@ -25,10 +25,13 @@ Submodules:
                  one-launch backward; condense_diff, mpc_box_model_diff,
                  mpc_box_loop_model_diff: the same with gradients of the
                  prediction model A, B, c; poly_solve_diff, mpc_poly_diff: the
-                 polytope QP and the state-constrained MPC step (all nine also
-                 exported here)
+                 polytope QP and the state-constrained MPC step;
+                 poly_loop_diff, mpc_poly_loop_diff: the one-launch
+                 state-constrained episode with a one-launch backward (all
+                 eleven also exported here)
   condense_diff  condense_vjp: the adjoint of condensing on the device
-  poly_diff      poly_solve_vjp, shared_grads: the adjoint of the polytope QP
+  poly_diff      poly_solve_vjp, shared_grads: the adjoint of the polytope QP;
+                 poly_loop_vjp, loop_shared_grads: that of its one-launch loop
 """
 from . import _native  # noqa: F401
 
@@ -36,7 +39,7 @@ __version__ = "0.1.0"
 
 _AUTOGRAD = ("solve_box_diff", "mpc_box_diff", "box_loop_diff", "mpc_box_loop_diff",
              "condense_diff", "mpc_box_model_diff", "mpc_box_loop_model_diff",
-             "poly_solve_diff", "mpc_poly_diff")
+             "poly_solve_diff", "mpc_poly_diff", "poly_loop_diff", "mpc_poly_loop_diff")
 __all__ = ["library_path", *_AUTOGRAD]
 
 

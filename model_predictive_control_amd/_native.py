@@ -116,6 +116,15 @@ _TABLE_POLY_DIFF = {
 SIGNATURES_POLY_DIFF = {name: (_KINDS[s[0]], [_KINDS[c] for c in s[1:].replace(" ", "")])
                         for name, s in _TABLE_POLY_DIFF.items()}
 
+# The symbols of include/mpcqp_poly_loop_diff.h (tests/test_poly_loop_vjp_host.py
+# checks them against that header).
+_TABLE_POLY_LOOP_DIFF = {
+    "mpcqp_mpc_poly_loop_vjp_workspace": "z iiiiii",
+    "mpcqp_mpc_poly_loop_vjp": "i iiiiiiii pppp pp pppp pppppp p pz p",
+}
+SIGNATURES_POLY_LOOP_DIFF = {name: (_KINDS[s[0]], [_KINDS[c] for c in s[1:].replace(" ", "")])
+                             for name, s in _TABLE_POLY_LOOP_DIFF.items()}
+
 ABI_VERSION = 1
 
 _lock = threading.Lock()
@@ -140,7 +149,8 @@ def load(path: str | None = None):
                 "(the HIP path has no CPU fallback)")
         lib = ctypes.CDLL(p)
         for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_DIFF.items(),
-                                  *SIGNATURES_POLY_DIFF.items()):
+                                  *SIGNATURES_POLY_DIFF.items(),
+                                  *SIGNATURES_POLY_LOOP_DIFF.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -45,6 +45,18 @@ With the active rows A = {i : y_i != 0} of C = [G; I], gz = dL/dz and gy = dL/dy
 
 A row at its bound with a zero multiplier counts as inactive (the one-sided
 derivative on the side that lets it leave).  m_total <= 64, nx <= 16.
+
+``poly_loop_diff`` and ``mpc_poly_loop_diff`` are the same for a whole
+state-constrained episode: the forward is ``batched.PolyQP.loop`` (one launch),
+the backward one launch of ``poly_diff.poly_loop_vjp``
+(include/mpcqp_poly_loop_diff.h ``mpcqp_mpc_poly_loop_vjp``; a second launch
+before it when the loss reads zs), the reverse-time recursion
+
+    lam <- gxs[T];  for t = T-1 .. 0:  gz = gzs[t] (+ gus[t] + B'lam on u_t),
+    eps_t, dL/dg_t as e, dL/df above at (z_t, y_t),  dL/de_t = -eps_t,
+    dL/dw_t = lam,  lam <- gxs[t] + A'lam + F' dL/dg_t - E' eps_t;  dL/dx0 = lam
+
+with the shared operands' gradients summed over the steps and the batch.
 """
 from __future__ import annotations
 
@@ -57,7 +69,7 @@ from . import poly_diff as _pdiff
 
 __all__ = ["solve_box_diff", "mpc_box_diff", "box_loop_diff", "mpc_box_loop_diff",
            "condense_diff", "mpc_box_model_diff", "mpc_box_loop_model_diff",
-           "poly_solve_diff", "mpc_poly_diff"]
+           "poly_solve_diff", "mpc_poly_diff", "poly_loop_diff", "mpc_poly_loop_diff"]
 
 MAX_N = batched.BOX_VJP_MAX_N
 
@@ -581,3 +593,134 @@ def mpc_poly_diff(A, B, Q, R, Qf, N, x0, xlo=None, xhi=None, lb=None, ub=None, *
     hl, hu = (None if h is None else h[None, :] - free for h in (hl, hu))
     return poly_solve_diff(H, Gam if rows else None, F, x0, None, hl, hu,
                            stage_bound(lb, nu, "lb"), stage_bound(ub, nu, "ub"), **kw)
+
+
+# ------------------------------------------------ the one-launch polytope loop
+def _step_grad(g, ref):
+    """The per-step, per-instance gradient ``g`` (T, b, w) for the operand
+    ``ref``: summed over the batch where ``ref`` is shared ((T, w))."""
+    return g if ref.ndim == 3 else g.sum(1)
+
+
+class _PolyLoop(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, H, G, F, A, B, x0, hl, hu, lbz, ubz, E, w, g, e, steps, qp, kw):
+        if qp is None:
+            qp = batched.PolyQP(H, G, F, lbz, ubz)
+        o = qp.loop(A, B, x0, steps, hl, hu, E, w, plans=True, multipliers=True, g=g, e=e, **kw)
+        xs, us, zs, ys, status = o["xs"], o["us"], o["zs"], o["ys"], o["status"]
+        ctx.mark_non_differentiable(status)
+        ctx.set_materialize_grads(False)
+        _stash(ctx, (A, B, xs, us, zs, ys, status), (hl, hu, lbz, ubz, E, g, e))
+        ctx.qp = qp
+        return xs, us, zs, ys, status
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gxs, gus, gzs, gys, _gstatus):
+        A, B, xs, us, zs, ys, status, hl, hu, lbz, ubz, E, g, e = _recover(ctx, 7)
+        qp = ctx.qp
+        # H, G, F, A, B, x0, hl, hu, lbz, ubz, E, w, g, e
+        nH, nG, nF, nA, nB, nx0, nhl, nhu, nlb, nub, nE, nw, ng, ne = ctx.needs_input_grad[:14]
+        m, dt = qp.m, zs.dtype
+        want = [k for k, nd in (("gx0", nx0), ("ghl", nhl or nlb), ("ghu", nhu or nub),
+                                ("geps", nG or nE or ne), ("gf", nH or nG or nF or ng),
+                                ("gw", nA or nB or nw)) if nd]
+        r = _pdiff.poly_loop_vjp(qp, A, B, ys,
+                                 *(None if t is None else t.to(dt) for t in (gxs, gus, gzs, gys)),
+                                 E=E, status=status, need=want)
+        shared = tuple(k for k, nd in (("gH", nH), ("gG", nG), ("gF", nF), ("gA", nA), ("gB", nB),
+                                       ("gE", nE)) if nd)
+        s = _pdiff.loop_shared_grads(qp, xs, us, zs, ys, r["gf"], r["geps"], r["gw"], r["vstatus"],
+                                     need=shared) if shared else {}
+        ghl = _batch_grad(r["ghl"][:, :m], hl) if nhl else None
+        ghu = _batch_grad(r["ghu"][:, :m], hu) if nhu else None
+        glbz = _bound_grad(r["ghl"][:, m:].sum(0), lbz, True) if nlb else None
+        gubz = _bound_grad(r["ghu"][:, m:].sum(0), ubz, True) if nub else None
+        gg = _step_grad(r["gf"], g) if ng else None
+        ge = _step_grad(-r["geps"][:, :, :m], e) if ne else None
+        return (s.get("gH"), s.get("gG"), s.get("gF"), s.get("gA"), s.get("gB"),
+                r["gx0"] if nx0 else None, ghl, ghu, glbz, gubz, s.get("gE"),
+                r["gw"] if nw else None, gg, ge, None, None, None)
+
+
+def poly_loop_diff(H, G, F, A, B, x0, hl=None, hu=None, lbz=None, ubz=None, *, steps, E=None,
+                   w=None, g=None, e=None, cold=False, max_iter=0, tol=0.0, qp=None):
+    """``batched.PolyQP(H, G, F, lbz, ubz).loop(A, B, x0, steps, hl, hu, E, w,
+    g=g, e=e, plans=True, multipliers=True)`` with gradients: returns ``(xs, us,
+    zs, ys, status)``, bit for bit the values of ``PolyQP.loop``, where xs (T+1,
+    b, nx), us (T, b, nu), zs (T, b, n) and ys (T, b, m_total) carry the graph
+    to x0 (b, nx), hl, hu ((m,) shared: summed over the batch, or (b, m)), g
+    ((T, n) or (T, b, n)), e ((T, m) or (T, b, m)), w (T, b, nx), tensor lbz /
+    ubz (Python-scalar bounds get none), packed H, G, F, E and the plant's A, B;
+    status is non-differentiable.  The backward pass is one launch of
+    ``poly_diff.poly_loop_vjp`` (after one product launch when the loss reads
+    zs) and, for the operands the episode shares, ``poly_diff.loop_shared_grads``.
+    An instance with a step that did not end OPTIMAL (or whose adjoint meets a
+    NaN or dependent active rows) contributes exact zeros to every gradient.
+    ``qp``: a ``PolyQP`` the caller built from the same H, G, F, lbz and ubz; it
+    skips the setup, and the gradients still go to the tensors passed here.
+    The soft loop has no adjoint: ``soft=`` is not accepted."""
+    kw = dict(cold=bool(cold), max_iter=int(max_iter), tol=float(tol))
+    return _PolyLoop.apply(H, G, F, A, B, x0, hl, hu, lbz, ubz, E, w, g, e, int(steps), qp, kw)
+
+
+def mpc_poly_loop_diff(A, B, Q, R, Qf, N, x0, xlo=None, xhi=None, lb=None, ub=None, *, steps,
+                       plant=None, w=None, x_ref=None, u_ref=None, cold=False, max_iter=0,
+                       tol=0.0):
+    """``batched.mpc_poly_loop`` (the one-launch episode of the linear MPC with
+    a state box on x_1..x_N and an input box) with gradients: returns ``(xs,
+    us, zs, ys, status)``, bit for bit the values of ``mpc_poly_loop(...,
+    plans=True, multipliers=True)``.  The ``PolyQP`` is built as there (the
+    shared model condensed once; G = Gam, E = Phi, the state box tiled over the
+    horizon) and ``poly_loop_diff`` runs the episode: gradients reach x0, xlo /
+    xhi (scalar, (nx,) or (N*nx,)) and lb / ub (scalar, (nu,) or (N*nu,)) given
+    as tensors, w, the references x_ref / u_ref (through
+    ``batched.tracking_terms``) and the simulated plant ``plant = (A_p, B_p)``.
+    The shared weights Q, R, Qf get theirs from one batch-1 call of
+    ``condense_diff.condense_vjp`` on dL/dH and dL/dF (exact: Gam and Phi do not
+    depend on them) plus, with a reference, the tracking term's, within the
+    limits nx <= 4, nu <= 2, N * nu <= 32: outside them weights that require grad
+    raise NotImplementedError.  So do a model A or B that require grad: their
+    gradient needs dL/dGam and dL/dPhi, which ``condense_vjp`` does not take."""
+    if _needs(A, B):
+        raise NotImplementedError(
+            "mpc_poly_loop_diff: gradients through the model's A and B need dL/dGam and dL/dPhi, "
+            "which the adjoint of condensing does not take; detach them (plant=(A_p, B_p) is "
+            "differentiated)")
+    N, T = int(N), int(steps)
+    dt, dev = batched._dt_dev(A)
+    A, B = batched._dev(A, dt, dev), batched._dev(B, dt, dev)
+    if A.ndim != 2 or B.ndim != 2:
+        raise ValueError("mpc_poly_loop_diff: the model (A, B) is shared by the batch")
+    nx, nu = int(B.shape[0]), int(B.shape[1])
+    outputs = ("H", "F", "Gam", "Phi")
+    if _needs(Q, R, Qf):
+        _model_limits("mpc_poly_loop_diff", nx, nu, N * nu)
+        A_, B_, Q, R, Qf = _plant_tensors(A, B, Q, R, Qf)
+        cd = _Condense.apply(A_, B_, Q, R, Qf, None, None, N, False, outputs)
+    else:
+        cd = tuple(batched.condense(A, B, Q, R, Qf, N, outputs=outputs)[k] for k in outputs)
+    H, F, Gam, Phi = (v[0] for v in cd)
+
+    def stage_bound(v, width, name):
+        if v is None:
+            return None
+        t = torch.as_tensor(v, dtype=dt, device=dev)
+        if t.ndim == 0 or tuple(t.shape) == (width,):
+            return t.expand(width).repeat(N)
+        if tuple(t.shape) == (N * width,):
+            return t
+        raise ValueError(f"{name}: expected a scalar, ({width},) or ({N * width},), "
+                         f"got {tuple(t.shape)}")
+
+    hl, hu = stage_bound(xlo, nx, "xlo"), stage_bound(xhi, nx, "xhi")
+    rows = hl is not None or hu is not None
+    g = None
+    if x_ref is not None or u_ref is not None:
+        g = batched.tracking_terms({"Gam": Gam}, *(batched._dev(v, dt, dev) for v in (Q, R, Qf)),
+                                   N, T, x_ref, u_ref)
+    Ap, Bp = (A, B) if plant is None else plant
+    return poly_loop_diff(H, Gam if rows else None, F, Ap, Bp, x0, hl, hu,
+                          stage_bound(lb, nu, "lb"), stage_bound(ub, nu, "ub"), steps=T,
+                          E=Phi if rows else None, w=w, g=g, cold=cold, max_iter=max_iter, tol=tol)

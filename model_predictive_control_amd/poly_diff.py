@@ -8,6 +8,13 @@ operands: gf (the extra gradient f), gx0, and ghl / ghu over all m_total rows of
 [G; I], whose rows m.. are the instance's share of dL/dlbz and dL/dubz.
 ``shared_grads`` forms the gradients of the operands the batch shares (H, F, G,
 lbz, ubz) from those, with torch products.
+
+``poly_loop_vjp`` is the same for a whole episode of ``PolyQP.loop``
+(include/mpcqp_poly_loop_diff.h ``mpcqp_mpc_poly_loop_vjp``): the reverse-time
+recursion over the steps in one launch, from the gradients with respect to xs,
+us, zs and ys to gx0, ghl / ghu summed over the episode and the per-step rows
+geps, gf = dL/dg_t and gw = dL/dw_t; ``loop_shared_grads`` forms the gradients
+of H, F, G, E, the plant A, B and lbz, ubz from those.
 """
 from __future__ import annotations
 
@@ -17,9 +24,12 @@ from . import _native as nat
 from . import batched
 from .batched import _alloc, _ptr, _stream
 
-__all__ = ["poly_solve_vjp", "scratch_bytes", "shared_grads", "VJP_OUTPUTS"]
+__all__ = ["poly_solve_vjp", "scratch_bytes", "shared_grads", "VJP_OUTPUTS",
+           "poly_loop_vjp", "loop_scratch_bytes", "loop_shared_grads", "LOOP_VJP_OUTPUTS"]
 
 VJP_OUTPUTS = ("gf", "gx0", "ghl", "ghu")
+LOOP_VJP_OUTPUTS = ("gx0", "ghl", "ghu", "geps", "gf", "gw")  # the order of the C prototype
+LOOP_SHARED = ("gH", "gF", "gG", "gE", "gA", "gB", "glbz", "gubz")
 
 
 def scratch_bytes(qp, batch: int) -> int:
@@ -124,5 +134,148 @@ def shared_grads(qp, x0, z, y, gf, e, vstatus, need=("gH", "gF", "gG", "glbz", "
         if "glbz" in need:
             o["glbz"] = torch.where(yb < 0, eb, torch.zeros_like(eb)).sum(0)
         if "gubz" in need:
+            o["gubz"] = torch.where(yb > 0, eb, torch.zeros_like(eb)).sum(0)
+    return o
+
+
+# ------------------------------------------------ the one-launch loop
+def loop_scratch_bytes(qp, batch: int, steps: int) -> int:
+    """Bytes of the ``scratch=`` buffer of ``poly_loop_vjp`` with gzs, for an
+    episode of ``steps`` steps of ``batch`` instances of ``qp``
+    (``mpcqp_mpc_poly_loop_vjp_workspace``)."""
+    return int(batched._lib().mpcqp_mpc_poly_loop_vjp_workspace(
+        batched._code(qp.dtype), int(batch), qp.n, qp.m, qp.nbox, int(steps)))
+
+
+def poly_loop_vjp(qp, A, B, ys, gxs=None, gus=None, gzs=None, gys=None, *, E=None, status=None,
+                  need=LOOP_VJP_OUTPUTS, scratch=None) -> dict:
+    """Adjoint of a whole episode of ``qp.loop`` (a ``batched.PolyQP``; hard,
+    with or without g / e), the reverse-time recursion in one launch (two with
+    gzs): include/mpcqp_poly_loop_diff.h ``mpcqp_mpc_poly_loop_vjp``.  ``A``
+    (nx, nx), ``B`` (nx, nu) and ``E`` (m, nx) or None are the plant and the row
+    shift the forward ran with; ``ys`` (T, b, m_total) and ``status`` (T, b)
+    what it returned (status None: every step counts as OPTIMAL); ``gxs``
+    (T+1, b, nx), ``gus`` (T, b, nu), ``gzs`` (T, b, n), ``gys`` (T, b, m_total)
+    the gradients of the loss with respect to xs, us, zs, ys, None meaning
+    zero.  Returns a dict with the entries of ``need`` (the others None) out of
+
+    * ``gx0`` (b, nx) = dL/dx0; ``ghl``, ``ghu`` (b, m_total), summed over the
+      episode: dL/dhl, dL/dhu on the rows below m and the instance's dL/dlbz,
+      dL/dubz on the rows from m on;
+    * ``geps`` (T, b, m_total), the row variable eps_t of every step (dL/de_t
+      = -geps[t][:, :m]); ``gf`` (T, b, n) = dL/dg_t; ``gw`` (T, b, nx) = dL/dw_t,
+
+    and ``vstatus`` (b,) int32: a bare STATUS_* code, the forward's at the first
+    step that did not end OPTIMAL (INFEASIBLE for a softened step), else
+    NOT_CONVEX (H not positive definite, or dependent active rows at some
+    step), NONFINITE, or OPTIMAL.  Every gradient of an instance whose vstatus
+    is not OPTIMAL is exactly zero, its per-step rows included.  ``scratch``: a
+    preallocated uint8 device buffer of ``loop_scratch_bytes(qp, b, T)`` bytes
+    (for graph capture); None allocates one when gzs is given."""
+    dt, dev = qp.dtype, qp.ws.device
+    unknown = set(need) - set(LOOP_VJP_OUTPUTS)
+    if unknown:
+        raise ValueError(f"need: unknown outputs {sorted(unknown)}")
+    n, m, mt, nx = qp.n, qp.m, qp.mt, qp.nx
+    if nx == 0:
+        raise ValueError("poly_loop_vjp needs a PolyQP with the x0 -> gradient map F")
+    A, B, E = batched._dev(A, dt, dev), batched._dev(B, dt, dev), batched._dev(E, dt, dev)
+    if tuple(A.shape) != (nx, nx):
+        raise ValueError(f"A must be ({nx}, {nx}), got {tuple(A.shape)}")
+    if B.ndim != 2 or B.shape[0] != nx:
+        raise ValueError(f"B must be ({nx}, nu), got {tuple(B.shape)}")
+    nu = int(B.shape[1])
+    if E is not None and tuple(E.shape) != (m, nx):
+        raise ValueError(f"E must be ({m}, {nx}), got {tuple(E.shape)}")
+    ys = batched._dev(ys, dt, dev)
+    if ys.ndim != 3 or ys.shape[2] != mt:
+        raise ValueError(f"ys must be (steps, batch, {mt}), got {tuple(ys.shape)}")
+    T, batch = int(ys.shape[0]), int(ys.shape[1])
+    gxs, gus, gzs, gys = (batched._dev(g, dt, dev) for g in (gxs, gus, gzs, gys))
+    for name, t, shape in (("gxs", gxs, (T + 1, batch, nx)), ("gus", gus, (T, batch, nu)),
+                           ("gzs", gzs, (T, batch, n)), ("gys", gys, (T, batch, mt))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    if status is not None and (status.dtype != torch.int32 or tuple(status.shape) != (T, batch)
+                               or not status.is_contiguous()):
+        raise ValueError(f"status must be a contiguous int32 tensor of shape ({T}, {batch})")
+    shapes = dict(gx0=(batch, nx), ghl=(batch, mt), ghu=(batch, mt), geps=(T, batch, mt),
+                  gf=(T, batch, n), gw=(T, batch, nx))
+    o = _alloc({**{k: (shapes[k], dt) if k in need else None for k in LOOP_VJP_OUTPUTS},
+                "vstatus": ((batch,), torch.int32)}, dev, keyed=True)
+    nbytes = loop_scratch_bytes(qp, batch, T) if gzs is not None else 0
+    if scratch is None and nbytes:
+        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    elif scratch is not None and (scratch.device.type != "cuda"
+                                  or scratch.numel() * scratch.element_size() < nbytes):
+        raise ValueError(f"scratch must be a device buffer of >= {nbytes} bytes")
+    rc = batched._lib().mpcqp_mpc_poly_loop_vjp(
+        batched._code(dt), batch, n, m, qp.nbox, nx, nu, T, _ptr(qp.ws), _ptr(E), _ptr(A), _ptr(B),
+        _ptr(ys), _ptr(status), _ptr(gxs), _ptr(gus), _ptr(gzs), _ptr(gys),
+        *(_ptr(o[k]) for k in LOOP_VJP_OUTPUTS), _ptr(o["vstatus"]), _ptr(scratch),
+        0 if scratch is None else scratch.numel() * scratch.element_size(), _stream())
+    nat.check(rc, "mpcqp_mpc_poly_loop_vjp")
+    return o
+
+
+def loop_shared_grads(qp, xs, us, zs, ys, gf, geps, gw, vstatus, need=LOOP_SHARED) -> dict:
+    """The gradients of the operands an episode shares over its steps and
+    instances, from the per-step results of ``poly_loop_vjp`` (``gf``, ``geps``,
+    ``gw``, ``vstatus``) and the forward's ``xs`` (T+1, b, nx), ``us``, ``zs``,
+    ``ys``: sums over all (t, b) rows.  With S = sum gf_t z_t':
+
+    * ``gH`` on the packed entries, folded: (i, j<i) = S_ij + S_ji, (i, i) = S_ii;
+    * ``gF`` (n, nx) = sum gf_t x_t';
+    * ``gG`` (m, n) = the rows below m of sum (y_t gf_t' - eps_t z_t'), ``gE`` (m,
+      nx) = -sum eps_t[:m] x_t' (both None for m = 0);
+    * ``gA`` (nx, nx) = sum gw_t x_t', ``gB`` (nx, nu) = sum gw_t u_t';
+    * ``glbz``, ``gubz`` (n,) = the sums of eps over the box rows held at their
+      lower / upper side (None without a box).
+
+    An entry of ``need`` whose per-step input (gf, geps or gw) is None raises.
+    The rows of every instance whose vstatus is not OPTIMAL are zeroed first:
+    the forward wrote NaN there, and 0 * NaN would poison the sums."""
+    unknown = set(need) - set(LOOP_SHARED)
+    if unknown:
+        raise ValueError(f"need: unknown gradients {sorted(unknown)}")
+    uses = dict(gH=("gf",), gF=("gf",), gG=("gf", "geps"), gE=("geps",), gA=("gw",), gB=("gw",),
+                glbz=("geps",), gubz=("geps",))
+    given = dict(gf=gf, geps=geps, gw=gw)
+    for k in need:
+        for u in uses[k]:
+            if given[u] is None:
+                raise ValueError(f"{k} needs {u}")
+    ok = (vstatus == nat.STATUS_OPTIMAL)[None, :, None]
+    T, n, m, nx = int(ys.shape[0]), qp.n, qp.m, qp.nx
+
+    def rows(t, width):
+        """(T * b, width) with the rows of failed instances zeroed"""
+        return None if t is None else torch.where(ok, t, torch.zeros_like(t)).reshape(-1, width)
+
+    x, u = rows(xs[:T], nx), rows(us, int(us.shape[-1]))
+    z, y = rows(zs, n), rows(ys, qp.mt)
+    gf, e, gw = rows(gf, n), rows(geps, qp.mt), rows(gw, nx)
+    o = dict.fromkeys(LOOP_SHARED)
+    if "gH" in need:
+        S = gf.transpose(0, 1) @ z
+        St = S + S.transpose(0, 1)
+        St = St - torch.diag(torch.diagonal(S))
+        o["gH"] = batched.pack_lower(St)
+    if "gF" in need:
+        o["gF"] = gf.transpose(0, 1) @ x
+    if "gG" in need and m > 0:
+        o["gG"] = y[:, :m].transpose(0, 1) @ gf - e[:, :m].transpose(0, 1) @ z
+    if "gE" in need and m > 0:
+        o["gE"] = -(e[:, :m].transpose(0, 1) @ x)
+    if "gA" in need:
+        o["gA"] = gw.transpose(0, 1) @ x
+    if "gB" in need:
+        o["gB"] = gw.transpose(0, 1) @ u
+    if qp.nbox:
+        if "glbz" in need:
+            yb, eb = y[:, m:], e[:, m:]
+            o["glbz"] = torch.where(yb < 0, eb, torch.zeros_like(eb)).sum(0)
+        if "gubz" in need:
+            yb, eb = y[:, m:], e[:, m:]
             o["gubz"] = torch.where(yb > 0, eb, torch.zeros_like(eb)).sum(0)
     return o
