@@ -219,17 +219,46 @@ struct QRowOwned<QSym<T, BS>> {
 #ifndef MPCQP_SWEEP_RD
 #define MPCQP_SWEEP_RD 1
 #endif
+// The trip's instruction stream (layouts with QTripLean), two more pieces with
+// the same kind of switch; neither changes an operand or an operation:
+//   MPCQP_SWEEP_FIX  the sweep writes row k and column k as moves under lane
+//                    masks instead of two select levels per entry (quad.hpp)
+//   MPCQP_RATE_ONCE  the multiplier rates mu_rate(st, co * rm, sgn) are formed
+//                    once per trip, in front of the filter; the filter, the
+//                    ratio test and the step update read them
+// Each alone gains little on the config-2 line and the two together 6 %
+// (with what was measured and rejected next to them).
+#ifndef MPCQP_SWEEP_FIX
+#define MPCQP_SWEEP_FIX 1
+#endif
+#ifndef MPCQP_RATE_ONCE
+#define MPCQP_RATE_ONCE 1
+#endif
+// Which layouts take them: fp64 BS = 5, the block size of the config-2 line
+// they were measured on.
+template <class Mat>
+struct QTripLean {
+  static constexpr bool v = false;
+};
+template <>
+struct QTripLean<QSym<double, 5>> {
+  static constexpr bool v = true;
+};
 
 // KEY: keyed reductions where the layout has them (QKeyed); a kernel passes
 // false to keep one instantiation on the compare-and-select reductions.
 // TRIP: the three pieces above where the rows are owned and keyed; a kernel
 // passes false to keep one instantiation on the general trip alone.
-template <class Mat_, bool OWN_ROWS = QRowOwned<Mat_>::v, bool KEY = true, bool TRIP = true>
+// LEAN: the two pieces of QTripLean where the layout takes them and the
+// kernel has the full-step trip; a kernel passes false to stay without them.
+template <class Mat_, bool OWN_ROWS = QRowOwned<Mat_>::v, bool KEY = true, bool TRIP = true,
+          bool LEAN = true>
 struct RowOwn {  // replicated
   using Mat = Mat_;
   static constexpr bool OWNED = false;
   static constexpr bool KEYED = false;
   static constexpr bool FAST = false, AHEAD = false, SWEEP_RD = false;
+  static constexpr bool SWEEP_FIX = false, RATE_ONCE = false;
   static constexpr int BS = Mat::RPL;
   static constexpr int RO = BS;
   // slot s holds a row; its matrix row, to compare with a pivot (-1: none)
@@ -256,8 +285,8 @@ struct RowOwn {  // replicated
   }
 };
 
-template <class Mat_, bool KEY, bool TRIP>
-struct RowOwn<Mat_, true, KEY, TRIP> {  // owned (QSym)
+template <class Mat_, bool KEY, bool TRIP, bool LEAN>
+struct RowOwn<Mat_, true, KEY, TRIP, LEAN> {  // owned (QSym)
   using Mat = Mat_;
   static constexpr bool OWNED = true;
   static constexpr int BS = Mat::RPL;
@@ -303,6 +332,9 @@ struct RowOwn<Mat_, true, KEY, TRIP> {  // owned (QSym)
   static constexpr bool FAST = TRIP && (KEYED ? MPCQP_FAST_TRIP != 0 : MPCQP_FAST_TRIP == 2);
   static constexpr bool AHEAD = TRIP && (KEYED ? MPCQP_BOUND_AHEAD != 0 : MPCQP_BOUND_AHEAD == 2);
   static constexpr bool SWEEP_RD = FAST && MPCQP_SWEEP_RD != 0;
+  static constexpr bool LEAN_TRIP = LEAN && FAST && KEYED && QTripLean<Mat>::v;
+  static constexpr bool SWEEP_FIX = LEAN_TRIP && MPCQP_SWEEP_FIX != 0;
+  static constexpr bool RATE_ONCE = LEAN_TRIP && MPCQP_RATE_ONCE != 0;
   using K = Key<key_bits(Mat::NMAX)>;
   template <bool MAX>
   static __device__ __forceinline__ void key_arg(double& key) {
@@ -392,6 +424,21 @@ __device__ __forceinline__ bool ratio_filter(const int (&st)[RO], const T (&mu)[
     const T dmu = mu_rate(st[r], co[r] * rm, sgn);
     const bool cand = (st[r] == 1 || st[r] == 2) && dmu < T(0);
     const T rhs = t2d * -dmu;
+    f = f || (cand && (mu[r] < rhs || rhs < RatioFilter<T>::TINY));
+  }
+  return f;
+}
+// The same on rates formed once per trip (RATE_ONCE): dmu[r] is the filter's
+// own mu_rate(st[r], co[r] * rm, sgn), so every word above holds unchanged.
+template <typename T, int RO>
+__device__ __forceinline__ bool ratio_filter(const int (&st)[RO], const T (&mu)[RO],
+                                             const T (&dmu)[RO], T t2) {
+  const T t2d = t2 * (T(1) + RatioFilter<T>::DELTA);
+  bool f = false;
+#pragma unroll
+  for (int r = 0; r < RO; ++r) {
+    const bool cand = (st[r] == 1 || st[r] == 2) && dmu[r] < T(0);
+    const T rhs = t2d * -dmu[r];
     f = f || (cand && (mu[r] < rhs || rhs < RatioFilter<T>::TINY));
   }
   return f;
@@ -536,6 +583,25 @@ struct SelKey {
                                             const double (&co)[RO], double rm, double sgn,
                                             double t2) const {
     return ratio_filter(st, mu, co, rm, sgn, t2) || !ratio_range(t2, K::big());
+  }
+  // ratio() and may_block() on the trip's rates dmu[r] = mu_rate(st[r],
+  // co[r] * rm, sgn) (RATE_ONCE)
+  __device__ __forceinline__ void ratio(const int (&st)[RO], const double (&mu)[RO],
+                                        const double (&dmu)[RO], double& ti, int& k) const {
+    double key = K::big();
+#pragma unroll
+    for (int r = 0; r < RO; ++r) {
+      const bool cand = (st[r] == 1 || st[r] == 2) && dmu[r] < 0.0;
+      const double t = cand ? fmin(-mu[r] * fast_rcp(dmu[r]), K::big()) : K::big();
+      key = key_min(key, K::pack(t, mi[r]));
+    }
+    Own::template key_arg<false>(key);
+    ti = K::clear(key);
+    k = K::code(key);
+  }
+  __device__ __forceinline__ bool may_block(const int (&st)[RO], const double (&mu)[RO],
+                                            const double (&dmu)[RO], double t2) const {
+    return ratio_filter(st, mu, dmu, t2) || !ratio_range(t2, K::big());
   }
   // the owners publish their rows of z; a new pivot reads z_p from there
   __device__ __forceinline__ void publish(const Mat& M, const double (&zr)[RO]) const {
@@ -709,11 +775,25 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
       [[maybe_unused]] T s_kr[BS], s_kcol[NC], s_sigma = T(-1), s_d = mpp;
       [[maybe_unused]] int s_idx = p;
       [[maybe_unused]] bool sweeping = false;
+      // RATE_ONCE: the multiplier rates of this trip, once for the filter, the
+      // ratio test and the step update (outside the filter's short-circuit)
+      [[maybe_unused]] T dmu[RO];
+      if constexpr (Own::RATE_ONCE) {
+#pragma unroll
+        for (int r = 0; r < RO; ++r) dmu[r] = mu_rate(st[r], co[r] * rm, sgn);
+      }
+      // some group of the wave may take a partial step (the ratio filter)
+      [[maybe_unused]] bool general = true;
+      if constexpr (Own::RATE_ONCE) {
+        general = __any(stepping && sel.may_block(st, mu, dmu, t2));
+      } else if constexpr (Own::FAST) {
+        general = __any(stepping && sel.may_block(st, mu, co, rm, sgn, t2));
+      }
       if constexpr (!Own::FAST) {
 #define MPCQP_TRIP_FULL false
 #include "gi_box_trip.inc"
 #undef MPCQP_TRIP_FULL
-      } else if (__any(stepping && sel.may_block(st, mu, co, rm, sgn, t2))) {
+      } else if (general) {
 #define MPCQP_TRIP_FULL false
 #include "gi_box_trip.inc"
 #undef MPCQP_TRIP_FULL
@@ -723,7 +803,12 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
 #undef MPCQP_TRIP_FULL
       }
       if constexpr (Own::FAST) {
-        if (sweeping) M.template sweep_col<Own::SWEEP_RD>(s_idx, s_sigma, s_d, s_kr, s_kcol);
+        if constexpr (Own::SWEEP_FIX) {
+          if (sweeping)
+            M.template sweep_col<Own::SWEEP_RD, true>(s_idx, s_sigma, s_d, s_kr, s_kcol);
+        } else {
+          if (sweeping) M.template sweep_col<Own::SWEEP_RD>(s_idx, s_sigma, s_d, s_kr, s_kcol);
+        }
       }
       MPCQP_PHASE(7);
     }

@@ -13,14 +13,18 @@
   constexpr bool FULL = MPCQP_TRIP_FULL;
   T ti = T(0);
   int k = 0;
-  if (!FULL) sel.ratio(st, mu, co, rm, sgn, ti, k);
+  if (!FULL) {
+    if constexpr (Own::RATE_ONCE) sel.ratio(st, mu, dmu, ti, k);
+    else sel.ratio(st, mu, co, rm, sgn, ti, k);
+  }
   const bool partial = !FULL && ti < t2;
   const T s_eff = stepping ? (partial ? ti : t2) : T(0);
 #pragma unroll
   for (int r = 0; r < RO; ++r) {
     const T cs = co[r] * rm;  // dz per unit move of z_p (c stays raw for the sweep)
     zr[r] = (st[r] == 0) ? fma(sgn * s_eff, cs, zr[r]) : zr[r];
-    mu[r] = fma(s_eff, mu_rate(st[r], cs, sgn), mu[r]);
+    if constexpr (Own::RATE_ONCE) mu[r] = fma(s_eff, dmu[r], mu[r]);
+    else mu[r] = fma(s_eff, mu_rate(st[r], cs, sgn), mu[r]);
   }
   gp = fma(-sgn * s_eff, rm, gp);  // d g_p / d z_p = -1 / M_pp
   zp = fma(sgn, s_eff, zp);

@@ -116,6 +116,17 @@ struct LoopTrip {
   static constexpr bool v = BS != 2;
 };
 
+// The masked sweep fix-up and the rates formed once per trip (RowOwn's LEAN,
+// gi_box_core.hpp) per instantiation.  The five fp64 BS = 5 kernels could take
+// them (269..279 + 13..23 -> 274..282 + 18..26 VGPRs + AGPRs, no scratch, one-wave
+// bound), but the config-2 loop line did not move with them (190.3 M, 190.3 -
+// 190.6, -> 190.9 M, 190.4 - 191.1 steps/s, ranges overlapping): no loop kernel
+// takes them, and all compile to the streams they had before.
+template <typename T, int NX, int NU, int BS, bool AFFINE>
+struct LoopLean {
+  static constexpr bool v = false;
+};
+
 // A wave-uniform pointer to global memory, held in scalar registers.
 template <typename T>
 using GlobalPtr = const __attribute__((address_space(1))) T*;
@@ -323,7 +334,7 @@ __global__ __launch_bounds__(64, (LoopOcc<T, BS>::w)) void box_loop_kernel(
     T zr[BS];
     int iters = 0;
     using Own = RowOwn<QSym<T, BS>, QRowOwned<QSym<T, BS>>::v, LoopKeyed<T, NX, NU, BS, AFFINE>::v,
-                       LoopTrip<T, NX, NU, BS, AFFINE>::v>;
+                       LoopTrip<T, NX, NU, BS, AFFINE>::v, LoopLean<T, NX, NU, BS, AFFINE>::v>;
     const int c2 = gi_box_st<true, Own>(M, gb, fs, lbs, ubs, n, a.max_iter, a.tol,
                                         live && code == MPCQP_STATUS_OPTIMAL, zr, iters,
                                         st MPCQP_CLK_ARG);

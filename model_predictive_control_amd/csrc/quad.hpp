@@ -33,6 +33,36 @@ __device__ __forceinline__ X quad_lane(X v) {
   return dpp<J | (J << 2) | (J << 4) | (J << 6)>(v);
 }
 
+// Five groups of five 64-bit moves, group i under the lane mask K[i] (a
+// ballot, so a subset of the lanes that execute this): D(i, j) = S[j], D(i, j)
+// being the lvalue of entry j of group i.  One statement that leaves exec as it
+// found it, with no compare and no branch inside (QSym::sweep_col<RD, true>).
+// The statement reads exec and must run under the control flow its ballots
+// were formed under.  Its operands do not say so: what holds it in place is
+// that device-side inline assembly is convergent to the compiler, which
+// therefore neither sinks nor hoists it across a divergent branch.  It is not
+// volatile (the measured instruction stream is that of the plain statement);
+// do not copy it to a place where that property does not hold.
+#define MPCQP_MOV5(I)                                                           \
+  "s_mov_b64 exec, %[k" #I "]\n\t"                                              \
+  "v_mov_b64 %[d" #I "0], %[s0]\n\tv_mov_b64 %[d" #I "1], %[s1]\n\t"            \
+  "v_mov_b64 %[d" #I "2], %[s2]\n\tv_mov_b64 %[d" #I "3], %[s3]\n\t"            \
+  "v_mov_b64 %[d" #I "4], %[s4]\n\t"
+#define MPCQP_MOV5_OUT(I, D)                                                   \
+  [d##I##0] "+v"(D(I, 0)), [d##I##1] "+v"(D(I, 1)), [d##I##2] "+v"(D(I, 2)),   \
+      [d##I##3] "+v"(D(I, 3)), [d##I##4] "+v"(D(I, 4))
+#define MPCQP_MASKED_MOV_5X5(D, K, S)                                          \
+  do {                                                                         \
+    unsigned long long mpcqp_exec;                                             \
+    asm("s_mov_b64 %[t], exec\n\t" MPCQP_MOV5(0) MPCQP_MOV5(1) MPCQP_MOV5(2)    \
+            MPCQP_MOV5(3) MPCQP_MOV5(4) "s_mov_b64 exec, %[t]"                 \
+        : [t] "=&s"(mpcqp_exec), MPCQP_MOV5_OUT(0, D), MPCQP_MOV5_OUT(1, D),   \
+          MPCQP_MOV5_OUT(2, D), MPCQP_MOV5_OUT(3, D), MPCQP_MOV5_OUT(4, D)     \
+        : [k0] "s"(K[0]), [k1] "s"(K[1]), [k2] "s"(K[2]), [k3] "s"(K[3]),      \
+          [k4] "s"(K[4]), [s0] "v"(S[0]), [s1] "v"(S[1]), [s2] "v"(S[2]),      \
+          [s3] "v"(S[3]), [s4] "v"(S[4]));                                     \
+  } while (0)
+
 template <typename T, int BS>
 struct QSym {
   static constexpr int NMAX = 4 * BS;
@@ -141,30 +171,66 @@ struct QSym {
   // full-step trip of gi_box_st).  One function with a flag and not a second
   // one that the first forwards to: forwarding changes the instruction streams
   // of five fp32 BS = 2 kernels that never pass RD.
-  template <bool RD = false>
+  // FIX: the same three candidates reach m[r][c] another way.  Every entry
+  // takes gen; then the lanes that hold column k overwrite it with scol and the
+  // lanes that hold row k overwrite that with srow (row k wins at (k, k), as in
+  // the nested select): BS 64-bit moves under the lane mask of one compare
+  // instead of two 32-bit selects per entry and level.  Same operands, same
+  // operations, same bits.  The moves are one inline-assembly statement per
+  // level that sets exec from the masks (MPCQP_MASKED_MOV_5X5): written as
+  // assignments under `if` the compiler selects again, and with only the move
+  // in assembly it builds ten regions of compare, saveexec and branch, which
+  // measured slower than the selects.
+  template <bool RD = false, bool FIX = false>
   __device__ __forceinline__ void sweep_col(int k, T sigma, T d, const T (&colr)[BS],
                                             const T (&colc)[BS]) {
     const T rd = RD ? d : fast_rcp(d);
     T a[BS], scol[BS], srow[BS];
-    bool ik[BS], jk[BS];
+    bool jk[BS];
+    if constexpr (FIX) {
+      static_assert(BS == 5 && sizeof(T) == 8, "the masked moves are written for 5 x 5 fp64");
+      unsigned long long ikm[BS], jkm[BS];
 #pragma unroll
-    for (int r = 0; r < BS; ++r) {
-      a[r] = colr[r] * rd;
-      scol[r] = sigma * a[r];
-      ik[r] = (bi * BS + r == k);
-    }
+      for (int r = 0; r < BS; ++r) {
+        a[r] = colr[r] * rd;
+        scol[r] = sigma * a[r];
+        ikm[r] = __builtin_amdgcn_ballot_w64(bi * BS + r == k);
 #pragma unroll
-    for (int c = 0; c < BS; ++c) {
-      jk[c] = (bj * BS + c == k);
-      srow[c] = jk[c] ? -rd : sigma * colc[c] * rd;
-    }
-#pragma unroll
-    for (int r = 0; r < BS; ++r)
+        for (int c = 0; c < BS; ++c) m[r][c] = fma(-a[r], colc[c], m[r][c]);
+      }
 #pragma unroll
       for (int c = 0; c < BS; ++c) {
-        const T gen = fma(-a[r], colc[c], m[r][c]);
-        m[r][c] = ik[r] ? srow[c] : (jk[c] ? scol[r] : gen);
+        jk[c] = (bj * BS + c == k);
+        jkm[c] = __builtin_amdgcn_ballot_w64(jk[c]);
+        srow[c] = jk[c] ? -rd : sigma * colc[c] * rd;
       }
+#define MPCQP_COL(I, J) m[J][I]
+#define MPCQP_ROW(I, J) m[I][J]
+      MPCQP_MASKED_MOV_5X5(MPCQP_COL, jkm, scol);
+      MPCQP_MASKED_MOV_5X5(MPCQP_ROW, ikm, srow);
+#undef MPCQP_COL
+#undef MPCQP_ROW
+    } else {
+      bool ik[BS];
+#pragma unroll
+      for (int r = 0; r < BS; ++r) {
+        a[r] = colr[r] * rd;
+        scol[r] = sigma * a[r];
+        ik[r] = (bi * BS + r == k);
+      }
+#pragma unroll
+      for (int c = 0; c < BS; ++c) {
+        jk[c] = (bj * BS + c == k);
+        srow[c] = jk[c] ? -rd : sigma * colc[c] * rd;
+      }
+#pragma unroll
+      for (int r = 0; r < BS; ++r)
+#pragma unroll
+        for (int c = 0; c < BS; ++c) {
+          const T gen = fma(-a[r], colc[c], m[r][c]);
+          m[r][c] = ik[r] ? srow[c] : (jk[c] ? scol[r] : gen);
+        }
+    }
   }
 
   __device__ __forceinline__ T sweep(int k, T sigma, T* gb) {

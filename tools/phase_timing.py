@@ -12,7 +12,7 @@ LIB = os.path.join(ROOT, "model_predictive_control_amd", "lib", "libmpcqp_timing
 SRCS = ["api.cpp", "condense.hip", "solve_box.hip", "solve_poly.hip", "mpc_box.hip", "quad_box.hip",
         "solve_qp.hip", "sweep.hip", "solve_pf.hip", "solve_zf.hip", "fallback64.hip", "mpc_qp.hip", "bicycle.hip", "misc.hip",
         "ipm.hip", "sqp.hip", "sqp_solve.hip", "loop_box.hip", "loop_poly.hip", "box_vjp.hip",
-        "loop_box_vjp.hip", "condense_vjp.hip", "poly_vjp.hip"]
+        "loop_box_vjp.hip", "condense_vjp.hip", "poly_vjp.hip", "loop_poly_vjp.hip"]
 # (config 2 is on the row form: phase 1 holds the W~ rows and the Pi recursion
 # as well, phase 2 only the f dot products and the barrier; the two-loop
 # instantiations spend phase 2 on the W~ columns and the adjoint)
