@@ -234,6 +234,27 @@ struct QRowOwned<QSym<T, BS>> {
 #ifndef MPCQP_RATE_ONCE
 #define MPCQP_RATE_ONCE 1
 #endif
+// Two more of the same kind, on the full-step trip's copies and waits:
+//   MPCQP_FULL_SWEEP       the full-step path sweeps inside the path, on the
+//                          pivot p with the column still in c / cc, 1 / d = rm
+//                          and the constant sigma = -1; no copy of the column
+//                          into the operands of a sweep behind the two paths,
+//                          no multiply by a register that holds -1.  The
+//                          sweep behind the paths serves the general one.
+//   MPCQP_PUBLISH_NODRAIN  the bound read-ahead (a_lb, a_ub, a_zp) is consumed
+//                          by every lane at the top of the trip, where its
+//                          reads finished long ago; without that the values
+//                          are pending at the pivot column's publish (their
+//                          only reader is a divergent block), their registers
+//                          are the column's address temporaries, and the
+//                          compiler drains the publish stores before it forms
+//                          the read addresses.
+#ifndef MPCQP_FULL_SWEEP
+#define MPCQP_FULL_SWEEP 1
+#endif
+#ifndef MPCQP_PUBLISH_NODRAIN
+#define MPCQP_PUBLISH_NODRAIN 1
+#endif
 // Which layouts take them: fp64 BS = 5, the block size of the config-2 line
 // they were measured on.
 template <class Mat>
@@ -259,6 +280,7 @@ struct RowOwn {  // replicated
   static constexpr bool KEYED = false;
   static constexpr bool FAST = false, AHEAD = false, SWEEP_RD = false;
   static constexpr bool SWEEP_FIX = false, RATE_ONCE = false;
+  static constexpr bool FULL_SWEEP = false, NODRAIN = false;
   static constexpr int BS = Mat::RPL;
   static constexpr int RO = BS;
   // slot s holds a row; its matrix row, to compare with a pivot (-1: none)
@@ -335,6 +357,9 @@ struct RowOwn<Mat_, true, KEY, TRIP, LEAN> {  // owned (QSym)
   static constexpr bool LEAN_TRIP = LEAN && FAST && KEYED && QTripLean<Mat>::v;
   static constexpr bool SWEEP_FIX = LEAN_TRIP && MPCQP_SWEEP_FIX != 0;
   static constexpr bool RATE_ONCE = LEAN_TRIP && MPCQP_RATE_ONCE != 0;
+  // (the path's own sweep is the masked-move one with 1 / d handed in)
+  static constexpr bool FULL_SWEEP = SWEEP_FIX && SWEEP_RD && MPCQP_FULL_SWEEP != 0;
+  static constexpr bool NODRAIN = LEAN_TRIP && AHEAD && MPCQP_PUBLISH_NODRAIN != 0;
   using K = Key<key_bits(Mat::NMAX)>;
   template <bool MAX>
   static __device__ __forceinline__ void key_arg(double& key) {
@@ -717,6 +742,12 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
     [[maybe_unused]] T a_lb = T(0), a_ub = T(0), a_zp = T(0);
     bool have_scan = false;
     while (true) {
+      if constexpr (Own::NODRAIN) {
+        // every lane takes the read-ahead here: an empty statement, whose
+        // operands make the compiler wait for the three reads now and not at
+        // the first reuse of their registers, behind the column's publish
+        asm volatile("" : : "v"(a_lb), "v"(a_ub), "v"(a_zp));
+      }
       if (__any(active && need_p)) {
         T viol, zv = T(0);
         int pi;
@@ -772,6 +803,9 @@ __device__ __forceinline__ int gi_box_st(Mat& M, T* gb, const T* fs, const T* lb
       // path M lived in two sets of registers, 169 -> 252 VGPRs at config 2)
       // and takes from them the pivot idx, sigma, the column kr / kcol and
       // d, or (SWEEP_RD) 1 / d, which the full-step path holds already.
+      // FULL_SWEEP: the full-step path sweeps inside itself, on c / cc, rm and
+      // sigma = -1 as they stand, and only the general path hands over to the
+      // sweep below; M still lives in one set of registers (204 -> 233 VGPRs).
       [[maybe_unused]] T s_kr[BS], s_kcol[NC], s_sigma = T(-1), s_d = mpp;
       [[maybe_unused]] int s_idx = p;
       [[maybe_unused]] bool sweeping = false;

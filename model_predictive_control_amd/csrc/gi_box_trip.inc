@@ -4,7 +4,8 @@
 //   false  the general trip;
 //   true   no group of the wave can take a partial step (the ratio filter):
 //          partial is the constant false and with it idx = p, sigma = -1 and
-//          the sweep column the pivot's; no ratio test, no second publish.
+//          the sweep column the pivot's; no ratio test, no second publish;
+//          with Own::FULL_SWEEP the path's own sweep on them, at its end.
 // Per group the arithmetic of a full step is the same on both, in the same
 // order.  Plain text and not a lambda or a helper template: either changes the
 // registers and the instruction streams of the kernels that have only the
@@ -82,7 +83,9 @@
     a_ub = ubs[pa];
     a_zp = sel.pivot_z(pa, a_zv);
   }
-  if constexpr (Own::FAST) {
+  if constexpr (Own::FULL_SWEEP && FULL) {
+    if (stepping && !bad) M.template sweep_col<true, true>(p, T(-1), rm, c, cc);
+  } else if constexpr (Own::FAST) {
     sweeping = stepping && !bad;
     s_idx = idx;
     s_sigma = sigma;
