@@ -539,6 +539,33 @@ def poly_solve_diff(H, G, F, x0=None, f=None, hl=None, hu=None, lbz=None, ubz=No
     return _PolySolve.apply(H, G, F, x0, f, hl, hu, lbz, ubz, qp, kw)
 
 
+def _mpc_poly_setup(who, refusal, A, B, Q, R, Qf, N, xlo, xhi, lb, ub):
+    """What ``mpc_poly_diff`` and ``mpc_poly_loop_diff`` do first: refuse A or B
+    that require grad (``refusal``: the caller's message), condense the shared
+    model once -- through ``_Condense`` when a weight requires grad, so that
+    H and F carry the graph to Q, R, Qf -- and tile the stage bounds over the
+    horizon.  Returns ``(dt, dev, A, B, (Q, R, Qf), (H, F, Gam, Phi), (hl, hu,
+    lbz, ubz))``; the weights are tensors (R a matrix) where they require grad,
+    as given otherwise."""
+    if _needs(A, B):
+        raise NotImplementedError(refusal)
+    dt, dev = batched._dt_dev(A)
+    A, B = batched._dev(A, dt, dev), batched._dev(B, dt, dev)
+    if A.ndim != 2 or B.ndim != 2:
+        raise ValueError(f"{who}: the model (A, B) is shared by the batch")
+    nx, nu = int(B.shape[0]), int(B.shape[1])
+    outputs = ("H", "F", "Gam", "Phi")
+    if _needs(Q, R, Qf):
+        _model_limits(who, nx, nu, N * nu)
+        A_, B_, Q, R, Qf = _plant_tensors(A, B, Q, R, Qf)
+        cd = _Condense.apply(A_, B_, Q, R, Qf, None, None, N, False, outputs)
+    else:
+        cd = tuple(batched.condense(A, B, Q, R, Qf, N, outputs=outputs)[k] for k in outputs)
+    bounds = tuple(batched._stage_bound(v, width, N, dt, dev, name) for v, width, name in (
+        (xlo, nx, "xlo"), (xhi, nx, "xhi"), (lb, nu, "lb"), (ub, nu, "ub")))
+    return dt, dev, A, B, (Q, R, Qf), tuple(v[0] for v in cd), bounds
+
+
 def mpc_poly_diff(A, B, Q, R, Qf, N, x0, xlo=None, xhi=None, lb=None, ub=None, **kw):
     """One step of the linear MPC with a state box on x_1..x_N and an input
     box (the problem ``batched.mpc_poly_loop`` solves at every step), with
@@ -555,44 +582,18 @@ def mpc_poly_diff(A, B, Q, R, Qf, N, x0, xlo=None, xhi=None, lb=None, ub=None, *
     weights that require grad raise NotImplementedError.  So do A or B that
     require grad: their gradient needs dL/dGam and dL/dPhi, which
     ``condense_vjp`` does not take."""
-    if _needs(A, B):
-        raise NotImplementedError(
-            "mpc_poly_diff: gradients through A and B need dL/dGam and dL/dPhi, which the "
-            "adjoint of condensing does not take; detach them")
-    N = int(N)
-    dt, dev = batched._dt_dev(A)
-    A, B = batched._dev(A, dt, dev), batched._dev(B, dt, dev)
-    if A.ndim != 2 or B.ndim != 2:
-        raise ValueError("mpc_poly_diff: the model (A, B) is shared by the batch")
-    nx, nu = int(B.shape[0]), int(B.shape[1])
-    outputs = ("H", "F", "Gam", "Phi")
-    if _needs(Q, R, Qf):
-        _model_limits("mpc_poly_diff", nx, nu, N * nu)
-        cd = _Condense.apply(*_plant_tensors(A, B, Q, R, Qf), None, None, N, False, outputs)
-    else:
-        cd = tuple(batched.condense(A, B, Q, R, Qf, N, outputs=outputs)[k] for k in outputs)
-    H, F, Gam, Phi = (v[0] for v in cd)
-
-    def stage_bound(v, width, name):
-        if v is None:
-            return None
-        t = torch.as_tensor(v, dtype=dt, device=dev)
-        if t.ndim == 0 or tuple(t.shape) == (width,):
-            return t.expand(width).repeat(N)
-        if tuple(t.shape) == (N * width,):
-            return t
-        raise ValueError(f"{name}: expected a scalar, ({width},) or ({N * width},), "
-                         f"got {tuple(t.shape)}")
-
+    dt, dev, A, B, _, (H, F, Gam, Phi), (hl, hu, lbz, ubz) = _mpc_poly_setup(
+        "mpc_poly_diff",
+        "mpc_poly_diff: gradients through A and B need dL/dGam and dL/dPhi, which the "
+        "adjoint of condensing does not take; detach them",
+        A, B, Q, R, Qf, int(N), xlo, xhi, lb, ub)
     x0 = torch.as_tensor(x0, dtype=dt, device=dev)
     if x0.ndim != 2:
-        raise ValueError(f"mpc_poly_diff: x0 must be (batch, {nx}), got {tuple(x0.shape)}")
-    hl, hu = stage_bound(xlo, nx, "xlo"), stage_bound(xhi, nx, "xhi")
+        raise ValueError(f"mpc_poly_diff: x0 must be (batch, {B.shape[0]}), got {tuple(x0.shape)}")
     rows = hl is not None or hu is not None
     free = x0 @ Phi.transpose(0, 1)
     hl, hu = (None if h is None else h[None, :] - free for h in (hl, hu))
-    return poly_solve_diff(H, Gam if rows else None, F, x0, None, hl, hu,
-                           stage_bound(lb, nu, "lb"), stage_bound(ub, nu, "ub"), **kw)
+    return poly_solve_diff(H, Gam if rows else None, F, x0, None, hl, hu, lbz, ubz, **kw)
 
 
 # ------------------------------------------------ the one-launch polytope loop
@@ -683,44 +684,17 @@ def mpc_poly_loop_diff(A, B, Q, R, Qf, N, x0, xlo=None, xhi=None, lb=None, ub=No
     limits nx <= 4, nu <= 2, N * nu <= 32: outside them weights that require grad
     raise NotImplementedError.  So do a model A or B that require grad: their
     gradient needs dL/dGam and dL/dPhi, which ``condense_vjp`` does not take."""
-    if _needs(A, B):
-        raise NotImplementedError(
-            "mpc_poly_loop_diff: gradients through the model's A and B need dL/dGam and dL/dPhi, "
-            "which the adjoint of condensing does not take; detach them (plant=(A_p, B_p) is "
-            "differentiated)")
     N, T = int(N), int(steps)
-    dt, dev = batched._dt_dev(A)
-    A, B = batched._dev(A, dt, dev), batched._dev(B, dt, dev)
-    if A.ndim != 2 or B.ndim != 2:
-        raise ValueError("mpc_poly_loop_diff: the model (A, B) is shared by the batch")
-    nx, nu = int(B.shape[0]), int(B.shape[1])
-    outputs = ("H", "F", "Gam", "Phi")
-    if _needs(Q, R, Qf):
-        _model_limits("mpc_poly_loop_diff", nx, nu, N * nu)
-        A_, B_, Q, R, Qf = _plant_tensors(A, B, Q, R, Qf)
-        cd = _Condense.apply(A_, B_, Q, R, Qf, None, None, N, False, outputs)
-    else:
-        cd = tuple(batched.condense(A, B, Q, R, Qf, N, outputs=outputs)[k] for k in outputs)
-    H, F, Gam, Phi = (v[0] for v in cd)
-
-    def stage_bound(v, width, name):
-        if v is None:
-            return None
-        t = torch.as_tensor(v, dtype=dt, device=dev)
-        if t.ndim == 0 or tuple(t.shape) == (width,):
-            return t.expand(width).repeat(N)
-        if tuple(t.shape) == (N * width,):
-            return t
-        raise ValueError(f"{name}: expected a scalar, ({width},) or ({N * width},), "
-                         f"got {tuple(t.shape)}")
-
-    hl, hu = stage_bound(xlo, nx, "xlo"), stage_bound(xhi, nx, "xhi")
+    dt, dev, A, B, (Q, R, Qf), (H, F, Gam, Phi), (hl, hu, lbz, ubz) = _mpc_poly_setup(
+        "mpc_poly_loop_diff",
+        "mpc_poly_loop_diff: gradients through the model's A and B need dL/dGam and dL/dPhi, "
+        "which the adjoint of condensing does not take; detach them (plant=(A_p, B_p) is "
+        "differentiated)", A, B, Q, R, Qf, N, xlo, xhi, lb, ub)
     rows = hl is not None or hu is not None
     g = None
     if x_ref is not None or u_ref is not None:
         g = batched.tracking_terms({"Gam": Gam}, *(batched._dev(v, dt, dev) for v in (Q, R, Qf)),
                                    N, T, x_ref, u_ref)
     Ap, Bp = (A, B) if plant is None else plant
-    return poly_loop_diff(H, Gam if rows else None, F, Ap, Bp, x0, hl, hu,
-                          stage_bound(lb, nu, "lb"), stage_bound(ub, nu, "ub"), steps=T,
+    return poly_loop_diff(H, Gam if rows else None, F, Ap, Bp, x0, hl, hu, lbz, ubz, steps=T,
                           E=Phi if rows else None, w=w, g=g, cold=cold, max_iter=max_iter, tol=tol)

@@ -1053,6 +1053,20 @@ def tracking_terms(cd, Q, R, Qf, N: int, T: int, x_ref=None, u_ref=None):
     return g.transpose(0, 1).contiguous() if g.ndim == 3 else g.contiguous()
 
 
+def _stage_bound(v, width: int, N: int, dt, dev, name: str):
+    """A stage bound (scalar or (width,)) tiled over the N stages, or (N * width,)
+    as it is; None stays None."""
+    if v is None:
+        return None
+    t = torch.as_tensor(v, dtype=dt, device=dev)
+    if t.ndim == 0 or tuple(t.shape) == (width,):
+        return t.expand(width).repeat(N)
+    if tuple(t.shape) == (N * width,):
+        return t
+    raise ValueError(f"{name}: expected a scalar, ({width},) or ({N * width},), "
+                     f"got {tuple(t.shape)}")
+
+
 def mpc_poly_loop(A, B, Q, R, Qf, N: int, x0, xlo=None, xhi=None, lb=None, ub=None,
                   steps: int = 1, *, plant=None, w=None, plans: bool = False,
                   multipliers: bool = False, cold: bool = False, max_iter: int = 0,
@@ -1081,28 +1095,18 @@ def mpc_poly_loop(A, B, Q, R, Qf, N: int, x0, xlo=None, xhi=None, lb=None, ub=No
     cd = condense(A, B, Q, R, Qf, N, outputs=("H", "F", "Gam", "Phi"))
     cd = {k: v[0] for k, v in cd.items()}
 
-    def stage_bound(v, width, name):
-        if v is None:
-            return None
-        t = torch.as_tensor(v, dtype=dt, device=dev)
-        if t.ndim == 0 or tuple(t.shape) == (width,):
-            return t.expand(width).repeat(N)
-        if tuple(t.shape) == (N * width,):
-            return t
-        raise ValueError(f"{name}: expected a scalar, ({width},) or ({N * width},), "
-                         f"got {tuple(t.shape)}")
-
-    hl, hu = stage_bound(xlo, nx, "xlo"), stage_bound(xhi, nx, "xhi")
+    hl, hu, lbz, ubz = (_stage_bound(v, width, N, dt, dev, name) for v, width, name in (
+        (xlo, nx, "xlo"), (xhi, nx, "xhi"), (lb, nu, "lb"), (ub, nu, "ub")))
     rows = hl is not None or hu is not None
-    qp = PolyQP(cd["H"], cd["Gam"] if rows else None, cd["F"], stage_bound(lb, nu, "lb"),
-                stage_bound(ub, nu, "ub"))
+    qp = PolyQP(cd["H"], cd["Gam"] if rows else None, cd["F"], lbz, ubz)
     Ap, Bp = (A, B) if plant is None else plant
     if soft is not None:
         if not isinstance(soft, (tuple, list)) or len(soft) != 2:
             raise ValueError("soft must be a pair (rho, sigma)")
         if not rows:
             raise ValueError("soft needs a state box (xlo or xhi)")
-        soft = (stage_bound(soft[0], nx, "soft rho"), stage_bound(soft[1], nx, "soft sigma"))
+        soft = (_stage_bound(soft[0], nx, N, dt, dev, "soft rho"),
+                _stage_bound(soft[1], nx, N, dt, dev, "soft sigma"))
     g = None
     if x_ref is not None or u_ref is not None:
         g = tracking_terms(cd, _dev(Q, dt, dev), _dev(R, dt, dev), _dev(Qf, dt, dev), N, steps,

@@ -21,34 +21,31 @@
 //         ghu += eps where y_t > 0,  ghl += eps where y_t < 0
 //         lam <- gxs[t] + A'lam + Kt gz - (L + [E; 0])_A' eps_A
 //     gx0 = lam
-// Only v, and through it Ut[:, :nu] v, Hinv[:, :nu] v and Kt[:, :nu] v, depend
-// on lam: the products with gzs[t] are hoisted.  -Hinv gzs[t] and -Ut gzs[t] of
-// all steps are one prior launch of poly_affine_prep_kernel (poly_prep.hpp)
-// over steps x batch rows into the caller's scratch; without gzs there is no
-// such launch and no scratch.  Kt gzs[t] is formed in the kernel, one step
-// ahead.
+// eps, the Ut' eps tail of gf, Kt gz and the L' eps tail of lam are the code of
+// poly_vjp_core.hpp, which poly_vjp_kernel calls too: on the same ys, gzs and
+// gys a step's eps and gf are those of mpcqp_poly_solve_vjp bit for bit, and
+// no round-off drifts over T.  Only v, and through it Ut[:, :nu] v,
+// Hinv[:, :nu] v and Kt[:, :nu] v, depend on lam: the products with gzs[t] are
+// hoisted.  -Hinv gzs[t] and -Ut gzs[t] of all steps are one prior launch of
+// poly_affine_prep_kernel (poly_prep.hpp) over steps x batch rows into the
+// caller's scratch; without gzs there is no such launch and no scratch.
+// Kt gzs[t] is formed in the kernel, one step ahead.
 //
 // On chip for the episode: packed M, L + [E; 0] (row-major: the adjoint reads
 // L' -- lane = state entry k, one active row r at a time -- so consecutive
 // lanes read consecutive words, where the forward's transposed copy would put
 // them NMAX words apart), A, B and the first nu columns of Ut and Kt in LDS;
 // lam (lane k holds entry k), the ghl / ghu accumulators and diag M (one row
-// per lane) in registers.  Per step W is reloaded from the LDS copy of M and
-// swept on the rows of A_t in ascending order with the forward's dependence
-// test, one sweep site, exactly as poly_vjp_kernel does: on the same ys, gzs
-// and gys a step's eps and gf are those of mpcqp_poly_solve_vjp bit for bit,
-// and no round-off drifts over T.  The rows of step t-1 that do not depend on
-// lam (ys, gys, -Ut gzs, gxs, gus, Kt gzs) are loaded before step t's sweeps,
-// the one-step-ahead pattern of loop_box_vjp.hip.
+// per lane) in registers.  Per step W is reloaded from the LDS copy of M
+// (poly_vjp_step).  The rows of step t-1 that do not depend on lam (ys, gys,
+// -Ut gzs, gxs, gus, Kt gzs) are loaded before step t's sweeps, the
+// one-step-ahead pattern of loop_box_vjp.hip.
 //
 // An instance whose outcome is not OPTIMAL gets exact zeros in every output,
 // its rows of geps, gf and gw included (rewritten in the epilogue by the lanes
-// that wrote them).  No atomics; every sum has a fixed order.  Built with the
-// approximate-division flags of loop_poly.hip: the pivot reciprocal is the
-// forward's fast_rcp.
-#include "dual_range_core.hpp"
+// that wrote them).  No atomics; every sum has a fixed order.
 #include "poly_prep.hpp"
-#include "poly_ws.hpp"
+#include "poly_vjp_core.hpp"
 
 #include "../../include/mpcqp_poly_loop_diff.h"
 
@@ -56,14 +53,8 @@ namespace mpcqp {
 
 // every upstream gradient, status, E and every output but vstatus may be null
 template <typename T>
-struct PolyLoopVjpArgs {
+struct PolyLoopVjpArgs : PolyFactors<T> {
   int batch, n, m, mt, nx, nu, steps;
-  const T* M;                  // packed lower mt x mt
-  const T* Hinv;               // n x n
-  const T* Ut;                 // mt x n
-  const T* Kt;                 // nx x n
-  const T* L;                  // mt x nx
-  const int32_t* flag;         // set by the shared inverse when H is not PD
   const T* E;                  // m x nx
   const T* A; const T* B;      // plant
   const T* ys;                 // steps x batch x mt
@@ -79,37 +70,12 @@ struct PolyLoopVjpArgs {
   int32_t* vstatus;
 };
 
-// Scratch of mpcqp_mpc_poly_loop_vjp: -Hinv gzs, then -Ut gzs, steps x batch rows.
-struct PolyLoopVjpWs {
-  int64_t R, oQ, oR, total;
-};
-static inline PolyLoopVjpWs poly_loop_vjp_ws(size_t es, int batch, int n, int mt, int steps) {
-  PolyLoopVjpWs w;
-  w.R = (int64_t)steps * batch;
-  w.oQ = 0;
-  w.oR = align256(w.R * n * (int64_t)es);
-  w.total = align256(w.oR + w.R * mt * (int64_t)es);
-  return w;
-}
-
 // LDS elements: Sym2D scratch, the mat-vec partials, packed M, L + [E; 0]
 // (NMAX x nx), A, B, the first nu columns of Ut (NMAX x nu) and Kt (nx x nu).
 __host__ __device__ inline int poly_loop_vjp_lds(int BS, int mt, int nx, int nu) {
   const int NMAX = 8 * BS;
   return NMAX * BS + NMAX + 8 * NMAX + mt * (mt + 1) / 2 + nx * NMAX + nx * nx + nx * nu +
          NMAX * nu + nx * nu;
-}
-
-// Sum over the wave in a fixed order; every lane receives the total.
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-  v += lane_step<1>(v);
-  v += lane_step<2>(v);
-  v += lane_step<4>(v);
-  v += lane_step<8>(v);
-  v += lane_step<16>(v);
-  v += lane_step<32>(v);
-  return v;
 }
 
 template <typename T, int BS>
@@ -196,18 +162,10 @@ __global__ __launch_bounds__(64) void poly_loop_vjp_kernel(PolyLoopVjpArgs<T> a)
     if (a.gxs && lane < nx) sn = a.gxs[rb * nx + lane];
     if (a.gus && lane < nu) un = a.gus[rb * nu + lane];
     if (a.gzs) {
-      // Kt gzs[t]: lane sums over j = lane, lane + 64, ..., one wave sum per k
       const T* gz = a.gzs + rb * nz;
       nfn = false;
       for (int j = lane; j < nz; j += kWave) nfn |= !finite(gz[j]) || !finite(a.nq[rb * nz + j]);
-      T gk = T(0);
-      for (int k = 0; k < nx; ++k) {
-        T s = T(0);
-        for (int j = lane; j < nz; j += kWave) s = fma(a.Kt[(int64_t)k * nz + j], gz[j], s);
-        s = wave_sum(s);
-        gk = (lane == k) ? s : gk;
-      }
-      kn = gk;
+      kn = kt_gz(a.Kt, gz, nz, nx, lane);
     }
   };
   const bool go = code0 == MPCQP_STATUS_OPTIMAL;
@@ -215,7 +173,6 @@ __global__ __launch_bounds__(64) void poly_loop_vjp_kernel(PolyLoopVjpArgs<T> a)
 
   S2 W;
   W.init(lane);
-  constexpr T dep_tol = kDualDepTol<T>;
 
   for (int t = go ? steps - 1 : -1; t >= 0; --t) {
     const int64_t rb = (int64_t)t * a.batch + b;
@@ -231,29 +188,15 @@ __global__ __launch_bounds__(64) void poly_loop_vjp_kernel(PolyLoopVjpArgs<T> a)
     if (t > 0) fetch(t - 1);
 
     const bool run = !nonfin && !notconv;
-    const bool act = run && row && yi != T(0);
-    const uint64_t amask = __builtin_amdgcn_ballot_w64(act);
     bool ok = run;
+    uint64_t emask = 0;
     T ei = T(0);
     if (run) {
-      bool unused = false;
+      bool unused = false;  // a NaN/Inf in M is not reported as such here
       W.load_packed(Ps, mt, unused);
-      for (uint64_t mk = amask; mk; mk &= mk - 1) {
-        const int k = uniform(__builtin_ctzll(mk));
-        T c[BS], cc[BS];
-        const T d = W.column(k, buf, c, cc);
-        if (!(d > dep_tol * fmax(readlane(md, k), T(1e-300)))) {
-          ok = false;
-          break;
-        }
-        W.sweep_col(k, T(1), d, c, cc);
-      }
+      ei = poly_vjp_step<T, BS>(W, buf, part, md, row && yi != T(0), ri - gyi, ok, emask);
       notconv = !ok;
-      // eps_A = M_AA^{-1} (r_A - gy_A) = -(W w)_A
-      const T wv = matvec_lane_lds<T, BS>(W, act ? ri - gyi : T(0), buf, part);
-      ei = (ok && act) ? -wv : T(0);
     }
-    const uint64_t emask = ok ? amask : 0;
     if (row) {
       if (a.geps) a.geps[rb * mt + lane] = ei;
       accl += yi < T(0) ? ei : T(0);
@@ -266,20 +209,13 @@ __global__ __launch_bounds__(64) void poly_loop_vjp_kernel(PolyLoopVjpArgs<T> a)
       for (int j = lane; j < nz; j += kWave) {
         T acc = a.nq ? a.nq[rb * nz + j] : T(0);
         for (int i = 0; i < nu; ++i) acc = fma(-a.Hinv[(int64_t)i * nz + j], readlane(v, i), acc);
-        for (uint64_t mk = emask; mk; mk &= mk - 1) {
-          const int r = uniform(__builtin_ctzll(mk));
-          acc = fma(a.Ut[(int64_t)r * nz + j], readlane(ei, r), acc);
-        }
-        a.gf[rb * nz + j] = acc;
+        a.gf[rb * nz + j] = gf_tail(a.Ut, nz, j, ei, emask, acc);
       }
     }
     // lam <- gxs[t] + A'lam + Kt gzs[t] + Kt[:, :nu] v - (L + [E; 0])_A' eps_A
     T ln = kg;
     for (int j = 0; j < nu; ++j) ln = fma(Kn[lk * nu + j], readlane(v, j), ln);
-    for (uint64_t mk = emask; mk; mk &= mk - 1) {
-      const int r = uniform(__builtin_ctzll(mk));
-      ln = fma(-LEs[r * nx + lk], readlane(ei, r), ln);
-    }
+    ln = lt_e_tail(LEs, nx, lk, ei, emask, ln);
     for (int i = 0; i < nx; ++i) ln = fma(As[i * nx + lk], readlane(lam, i), ln);
     lam = lane < nx ? ln + sx : T(0);
   }
@@ -323,20 +259,13 @@ static int launch_poly_loop_vjp(const PolyLoopVjpArgs<T>& a, hipStream_t st) {
   return MPCQP_OK;
 }
 
-static bool poly_loop_vjp_sizes_ok(int dtype, int batch, int n, int m, int nbox, int steps) {
-  const int mt = m + (nbox ? n : 0);
-  return (dtype == MPCQP_F64 || dtype == MPCQP_F32) && batch >= 0 && n >= 1 && m >= 0 &&
-         steps >= 0 && mt >= 1 && mt <= 64;
-}
-
 }  // namespace mpcqp
 
 extern "C" size_t mpcqp_mpc_poly_loop_vjp_workspace(int dtype, int batch, int n, int m, int nbox,
                                                     int steps) {
-  if (!mpcqp::poly_loop_vjp_sizes_ok(dtype, batch, n, m, nbox, steps)) return 0;
-  return (size_t)mpcqp::poly_loop_vjp_ws(mpcqp::dtype_size(dtype), batch, n, m + (nbox ? n : 0),
-                                         steps)
-      .total;
+  const int mt = m + (nbox ? n : 0);
+  if (!mpcqp::poly_vjp_sizes_ok(dtype, n, m, mt) || batch < 0 || steps < 0) return 0;
+  return (size_t)mpcqp::poly_vjp_ws(mpcqp::dtype_size(dtype), (int64_t)steps * batch, n, mt).total;
 }
 
 // The argument checks, all before any device work.
@@ -360,7 +289,8 @@ extern "C" int mpcqp_mpc_poly_loop_vjp(int dtype, int batch, int n, int m, int n
   MPCQP_CHECK_ARG(workspace && A && Bm && vstatus, "%s: workspace, A, B and vstatus are required",
                   who);
   MPCQP_CHECK_ARG(steps == 0 || ys, "%s: ys is required for steps > 0", who);
-  const PolyLoopVjpWs S = poly_loop_vjp_ws(dtype_size(dtype), batch, n, mt, steps);
+  const int64_t rows = (int64_t)steps * batch;
+  const PolyVjpWs S = poly_vjp_ws(dtype_size(dtype), rows, n, mt);
   const bool prep = gzs && steps > 0;
   MPCQP_CHECK_ARG(!prep || (scratch && scratch_bytes >= (size_t)S.total),
                   "%s: gzs needs %lld B of scratch, %zu given", who, (long long)S.total,
@@ -369,7 +299,7 @@ extern "C" int mpcqp_mpc_poly_loop_vjp(int dtype, int batch, int n, int m, int n
   const PolyWs L = poly_ws(dtype_size(dtype), n, mt, nx);
   const char* base = (const char*)workspace;
   if (prep) {
-    const int rc = launch_poly_affine_prep(who, dtype, gzs, S.R, n, mt, base + L.oHinv,
+    const int rc = launch_poly_affine_prep(who, dtype, gzs, rows, n, mt, base + L.oHinv,
                                            base + L.oUt, (char*)scratch + S.oQ,
                                            (char*)scratch + S.oR, st);
     if (rc != MPCQP_OK) return rc;
@@ -377,10 +307,8 @@ extern "C" int mpcqp_mpc_poly_loop_vjp(int dtype, int batch, int n, int m, int n
   auto run = [&](auto tp) {
     using T = decltype(tp);
     PolyLoopVjpArgs<T> a;
+    set_poly_factors<T>(a, workspace, L);
     a.batch = batch; a.n = n; a.m = m; a.mt = mt; a.nx = nx; a.nu = nu; a.steps = steps;
-    a.M = (const T*)(base + L.oM); a.Hinv = (const T*)(base + L.oHinv);
-    a.Ut = (const T*)(base + L.oUt); a.Kt = (const T*)(base + L.oKt);
-    a.L = (const T*)(base + L.oL); a.flag = (const int32_t*)(base + L.oFlag);
     a.E = m > 0 ? (const T*)E : nullptr; a.A = (const T*)A; a.B = (const T*)Bm;
     a.ys = (const T*)ys; a.status = status;
     a.gxs = (const T*)gxs; a.gus = (const T*)gus; a.gys = (const T*)gys;

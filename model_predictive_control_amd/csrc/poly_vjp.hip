@@ -1,39 +1,22 @@
 // poly_vjp.hip -- the adjoint of the stand-alone polytope QP
 // (mpcqp_poly_solve_vjp, include/mpcqp_poly_diff.h), one instance per
-// wavefront on the Sym2D register grid of the forward (solve_poly.hip).
-//
-// At the optimum of  min 1/2 z'Hz + f'z,  l <= C z <= u,  C = [G; I],  the
-// forward wrote the signed multipliers y with an exact 0 on every inactive
-// row: A = {i : y_i != 0}, the side is the sign of y_i.  On A the KKT system
-// is  H z + f + C_A' y_A = 0,  C_A z = b_A;  with gz = dL/dz, gy = dL/dy and the
-// shared factors of mpcqp_poly_setup (Hinv, Ut = C Hinv, M = C Hinv C',
-// Kt = (-Hinv F)', L = -Ut F):
-//     q   = Hinv gz,  r = Ut gz
-//     e_A = M_AA^{-1} (r_A - gy_A),  e = 0 elsewhere
-//     gf  = -(q - Ut_A' e_A)                 dL/df1
-//     gx0 = Kt gz - L_A' e_A  (= F' gf)      dL/dx0
-//     ghu_i = e_i (y_i > 0),  ghl_i = e_i (y_i < 0)
-// Two launches:
+// wavefront on the Sym2D register grid of the forward (solve_poly.hip).  The
+// algebra and the step itself are in poly_vjp_core.hpp; here are the two
+// launches, the staging and the status rules.
 //   1. q and r of every instance: the skinny GEMM poly_affine_prep_kernel of
 //      loop_poly.hip (poly_prep.hpp), which writes -Hinv gz and -Ut gz into the
 //      caller's scratch; an element of Hinv / Ut is loaded once per 16
 //      instances, not once per instance.
-//   2. poly_vjp_kernel: M staged and loaded as the forward does, swept on the
-//      rows of A in ascending order.  The forward's refresh() has v = W w,
-//      y_A = -v_A for w_A = s0_A - b_A, and y_A = M_AA^{-1} (s0_A - b_A), so
-//      W_AA = -M_AA^{-1}:  e_A = -(W w)_A  with  w_A = r_A - gy_A, 0 elsewhere
-//      -- |A| sweeps and one mat-vec, no iterations.  Row vectors (y, gy, r,
-//      e, diag M) one row per lane; gf over lanes strided by 64 in j, the
-//      forward epilogue's loop with readlane(e, r).
-// A pivot at or below kDualDepTol M_kk (the forward's dependence test) means
-// the rows marked active are dependent: NOT_CONVEX, every output zero.  An
-// instance whose vstatus is not OPTIMAL gets exact zeros in every output (a
-// NaN would poison the batch sum of a shared operand's gradient).  No atomics;
-// every sum has a fixed order.  Built with the approximate-division flags of
-// solve_poly.hip: the pivot reciprocal is the forward's fast_rcp.
-#include "dual_range_core.hpp"
+//   2. poly_vjp_kernel: M staged as the forward does, one poly_vjp_step, then
+//      ghu_i = e_i (y_i > 0), ghl_i = e_i (y_i < 0), gf = -q + Ut_A' e_A over
+//      lanes strided by 64 in j, gx0 = Kt gz - L_A' e_A.
+// vstatus: the forward's code if that is not OPTIMAL, else NOT_CONVEX (H not
+// positive definite), NONFINITE (an input or M), NOT_CONVEX (the rows marked
+// active are dependent).  An instance whose vstatus is not OPTIMAL gets exact
+// zeros in every output (a NaN would poison the batch sum of a shared
+// operand's gradient).  No atomics; every sum has a fixed order.
 #include "poly_prep.hpp"
-#include "poly_ws.hpp"
+#include "poly_vjp_core.hpp"
 
 #include "../../include/mpcqp_poly_diff.h"
 
@@ -41,13 +24,8 @@ namespace mpcqp {
 
 // status, gz (with nq, nr), gy and every output may be null
 template <typename T>
-struct PolyVjpArgs {
+struct PolyVjpArgs : PolyFactors<T> {
   int batch, n, mt, nx;        // nx = 0 without gx0
-  const T* M;                  // packed lower mt x mt
-  const T* Ut;                 // mt x n
-  const T* Kt;                 // nx x n
-  const T* L;                  // mt x nx
-  const int32_t* flag;         // set by the shared inverse when H is not PD
   const T* y;
   const int32_t* status;
   const T* gz;
@@ -57,30 +35,6 @@ struct PolyVjpArgs {
   T *gf, *gx0, *ghl, *ghu;
   int32_t* vstatus;
 };
-
-// Scratch of mpcqp_poly_solve_vjp: -q, then -r.
-struct PolyVjpWs {
-  int64_t oQ, oR, total;
-};
-static inline PolyVjpWs poly_vjp_ws(size_t es, int batch, int n, int mt) {
-  PolyVjpWs w;
-  w.oQ = 0;
-  w.oR = align256((int64_t)batch * n * (int64_t)es);
-  w.total = align256(w.oR + (int64_t)batch * mt * (int64_t)es);
-  return w;
-}
-
-// Sum over the wave in a fixed order; every lane receives the total.
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-  v += lane_step<1>(v);
-  v += lane_step<2>(v);
-  v += lane_step<4>(v);
-  v += lane_step<8>(v);
-  v += lane_step<16>(v);
-  v += lane_step<32>(v);
-  return v;
-}
 
 template <typename T, int BS>
 __global__ __launch_bounds__(64) void poly_vjp_kernel(PolyVjpArgs<T> a) {
@@ -117,7 +71,7 @@ __global__ __launch_bounds__(64) void poly_vjp_kernel(PolyVjpArgs<T> a) {
   }
   S2 W;
   W.init(lane);
-  W.load_packed(Ps, mt, nonfinite);
+  W.load_packed(Ps, mt, nonfinite);  // a NaN/Inf in M counts as NONFINITE here
 
   // The forward's own failure goes first: it wrote NaN into y and z, and
   // NONFINITE here would hide the cause.
@@ -127,24 +81,12 @@ __global__ __launch_bounds__(64) void poly_vjp_kernel(PolyVjpArgs<T> a) {
     else if (__any(nonfinite)) code = MPCQP_STATUS_NONFINITE;
   }
   code = uniform(code);
-  bool act = code == MPCQP_STATUS_OPTIMAL && row && yi != T(0);
-  const uint64_t amask = __builtin_amdgcn_ballot_w64(act);
-  constexpr T dep_tol = kDualDepTol<T>;
-  for (uint64_t mk = amask; mk; mk &= mk - 1) {
-    const int k = uniform(__builtin_ctzll(mk));
-    T c[BS], cc[BS];
-    const T d = W.column(k, buf, c, cc);
-    if (!(d > dep_tol * fmax(readlane(md, k), T(1e-300)))) {
-      code = MPCQP_STATUS_NOT_CONVEX;
-      break;
-    }
-    W.sweep_col(k, T(1), d, c, cc);
-  }
+  const bool act = code == MPCQP_STATUS_OPTIMAL && row && yi != T(0);
+  bool swept;
+  uint64_t emask;
+  const T ei = poly_vjp_step<T, BS>(W, buf, part, md, act, ri - gyi, swept, emask);
+  if (!swept) code = MPCQP_STATUS_NOT_CONVEX;
   const bool ok = code == MPCQP_STATUS_OPTIMAL;
-  // e_A = M_AA^{-1} (r_A - gy_A) = -(W w)_A
-  const T v = matvec_lane_lds<T, BS>(W, act ? ri - gyi : T(0), buf, part);
-  const T ei = (ok && act) ? -v : T(0);
-  const uint64_t emask = ok ? amask : 0;
   if (row) {
     const int64_t o = (int64_t)b * mt + lane;
     if (a.ghl) a.ghl[o] = yi < T(0) ? ei : T(0);
@@ -155,32 +97,15 @@ __global__ __launch_bounds__(64) void poly_vjp_kernel(PolyVjpArgs<T> a) {
     for (int j = lane; j < nz; j += kWave) {
       const int64_t o = (int64_t)b * nz + j;
       const T qj = a.nq ? -a.nq[o] : T(0);
-      T acc = -qj;
-      for (uint64_t mk = emask; mk; mk &= mk - 1) {
-        const int r = uniform(__builtin_ctzll(mk));
-        acc = fma(a.Ut[(int64_t)r * nz + j], readlane(ei, r), acc);
-      }
+      const T acc = gf_tail(a.Ut, nz, j, ei, emask, -qj);
       a.gf[o] = ok ? acc : T(0);
     }
   }
-  // gx0_k = sum_j Kt[k][j] gz_j - sum over A of L[r][k] e_r: lane sums over
-  // j = lane, lane + 64, ..., one wave sum per k, lane k keeps entry k
+  // gx0_k = sum_j Kt[k][j] gz_j - sum over A of L[r][k] e_r
   if (a.gx0) {
-    T gk = T(0);
-    for (int k = 0; k < nx; ++k) {
-      T s = T(0);
-      for (int j = lane; j < nz; j += kWave) {
-        const T gzj = a.gz ? a.gz[(int64_t)b * nz + j] : T(0);
-        s = fma(a.Kt[(int64_t)k * nz + j], gzj, s);
-      }
-      s = wave_sum(s);
-      gk = (lane == k) ? s : gk;
-    }
+    T gk = kt_gz(a.Kt, a.gz ? a.gz + (int64_t)b * nz : nullptr, nz, nx, lane);
     if (lane < nx) {
-      for (uint64_t mk = emask; mk; mk &= mk - 1) {
-        const int r = uniform(__builtin_ctzll(mk));
-        gk = fma(-a.L[r * nx + lane], readlane(ei, r), gk);
-      }
+      gk = lt_e_tail(a.L, nx, lane, ei, emask, gk);
       a.gx0[(int64_t)b * nx + lane] = ok ? gk : T(0);
     }
   }
@@ -200,9 +125,7 @@ static int launch_poly_vjp(const PolyVjpArgs<T>& a, hipStream_t st) {
 
 extern "C" size_t mpcqp_poly_solve_vjp_workspace(int dtype, int batch, int n, int m, int nbox) {
   const int mt = m + (nbox ? n : 0);
-  if ((dtype != MPCQP_F64 && dtype != MPCQP_F32) || batch <= 0 || n < 1 || m < 0 || mt < 1 ||
-      mt > 64)
-    return 0;
+  if (!mpcqp::poly_vjp_sizes_ok(dtype, n, m, mt) || batch <= 0) return 0;
   return (size_t)mpcqp::poly_vjp_ws(mpcqp::dtype_size(dtype), batch, n, mt).total;
 }
 
@@ -241,10 +164,8 @@ extern "C" int mpcqp_poly_solve_vjp(int dtype, int batch, int n, int m, int nbox
   auto run = [&](auto tp) {
     using T = decltype(tp);
     PolyVjpArgs<T> a;
+    set_poly_factors<T>(a, workspace, L);
     a.batch = batch; a.n = n; a.mt = mt; a.nx = gx0 ? nx : 0;
-    a.M = (const T*)(base + L.oM); a.Ut = (const T*)(base + L.oUt);
-    a.Kt = (const T*)(base + L.oKt); a.L = (const T*)(base + L.oL);
-    a.flag = (const int32_t*)(base + L.oFlag);
     a.y = (const T*)y; a.status = status;
     a.gz = (const T*)gz; a.gy = (const T*)gy;
     a.nq = gz ? (const T*)((const char*)scratch + S.oQ) : nullptr;

@@ -32,6 +32,50 @@ LOOP_VJP_OUTPUTS = ("gx0", "ghl", "ghu", "geps", "gf", "gw")  # the order of the
 LOOP_SHARED = ("gH", "gF", "gG", "gE", "gA", "gB", "glbz", "gubz")
 
 
+def _scratch_arg(scratch, nbytes: int, dev):
+    """The ``scratch=`` buffer to pass on: a fresh one of ``nbytes`` bytes when
+    none was given and some are needed, else the caller's, checked."""
+    if scratch is None and nbytes:
+        return torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    if scratch is not None and (scratch.device.type != "cuda"
+                                or scratch.numel() * scratch.element_size() < nbytes):
+        raise ValueError(f"scratch must be a device buffer of >= {nbytes} bytes")
+    return scratch
+
+
+def _pack_fold(S):
+    """dL/dH on the packed entries from the full, unsymmetrised S = sum gf z':
+    (i, j<i) = S_ij + S_ji, (i, i) = S_ii."""
+    St = S + S.transpose(0, 1)
+    St = St - torch.diag(torch.diagonal(S))
+    return batched.pack_lower(St)
+
+
+def _row_grads(qp, need, z, y, gf, e, x=None, u=None, gw=None) -> dict:
+    """The shared operands' gradients as sums over flattened rows (one per
+    instance, or per step and instance; failed ones already zeroed): gH, gG,
+    glbz, gubz, with ``x`` gF and gE, with ``gw`` gA and gB.  An entry not in
+    ``need``, or whose operand ``qp`` does not have, is None."""
+    m, o = qp.m, dict.fromkeys(LOOP_SHARED)
+    if "gH" in need:
+        o["gH"] = _pack_fold(gf.transpose(0, 1) @ z)
+    if "gF" in need and x is not None:
+        o["gF"] = gf.transpose(0, 1) @ x
+    if "gG" in need and m > 0:
+        o["gG"] = y[:, :m].transpose(0, 1) @ gf - e[:, :m].transpose(0, 1) @ z
+    if "gE" in need and m > 0:
+        o["gE"] = -(e[:, :m].transpose(0, 1) @ x)
+    if "gA" in need:
+        o["gA"] = gw.transpose(0, 1) @ x
+    if "gB" in need:
+        o["gB"] = gw.transpose(0, 1) @ u
+    if qp.nbox and "glbz" in need:
+        o["glbz"] = torch.where(y[:, m:] < 0, e[:, m:], torch.zeros_like(e[:, m:])).sum(0)
+    if qp.nbox and "gubz" in need:
+        o["gubz"] = torch.where(y[:, m:] > 0, e[:, m:], torch.zeros_like(e[:, m:])).sum(0)
+    return o
+
+
 def scratch_bytes(qp, batch: int) -> int:
     """Bytes of the ``scratch=`` buffer of ``poly_solve_vjp`` for ``batch``
     instances of ``qp`` (``mpcqp_poly_solve_vjp_workspace``)."""
@@ -77,12 +121,7 @@ def poly_solve_vjp(qp, y, gz=None, gy=None, *, status=None, need=VJP_OUTPUTS, sc
     shapes = dict(gf=(batch, qp.n), gx0=(batch, qp.nx), ghl=(batch, qp.mt), ghu=(batch, qp.mt))
     o = _alloc({**{k: (shapes[k], dt) if k in need else None for k in VJP_OUTPUTS},
                 "vstatus": ((batch,), torch.int32)}, dev, keyed=True)
-    nbytes = scratch_bytes(qp, batch) if gz is not None else 0
-    if scratch is None and nbytes:
-        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    elif scratch is not None and (scratch.device.type != "cuda"
-                                  or scratch.numel() * scratch.element_size() < nbytes):
-        raise ValueError(f"scratch must be a device buffer of >= {nbytes} bytes")
+    scratch = _scratch_arg(scratch, scratch_bytes(qp, batch) if gz is not None else 0, dev)
     rc = batched._lib().mpcqp_poly_solve_vjp(
         batched._code(dt), batch, qp.n, qp.m, qp.nbox, qp.nx, _ptr(qp.ws), _ptr(y), _ptr(status),
         _ptr(gz), _ptr(gy), *(_ptr(o[k]) for k in VJP_OUTPUTS), _ptr(o["vstatus"]),
@@ -109,32 +148,18 @@ def shared_grads(qp, x0, z, y, gf, e, vstatus, need=("gH", "gF", "gG", "glbz", "
     The rows of z, y (and x0) of every instance whose vstatus is not OPTIMAL are
     zeroed first: the forward wrote NaN there, and 0 * NaN would poison the sums."""
     ok = (vstatus == nat.STATUS_OPTIMAL)[:, None]
-    batch, n, m = int(z.shape[0]), qp.n, qp.m
+    batch = int(z.shape[0])
 
     def keep(t):
         return torch.where(ok, t, torch.zeros_like(t))
 
-    z, y, gf, e = keep(z), keep(y), keep(gf), keep(e)
-    o = dict.fromkeys(("gH", "gF", "gG", "glbz", "gubz"))
-    if "gH" in need:
-        S = gf.transpose(0, 1) @ z
-        St = S + S.transpose(0, 1)
-        St = St - torch.diag(torch.diagonal(S))
-        o["gH"] = batched.pack_lower(St)
-    if "gF" in need and qp.nx > 0:
-        if x0 is None:
-            o["gF"] = torch.zeros((n, qp.nx), dtype=z.dtype, device=z.device)
-        else:
-            x0 = keep(x0.expand(batch, qp.nx))
-            o["gF"] = gf.transpose(0, 1) @ x0
-    if "gG" in need and m > 0:
-        o["gG"] = y[:, :m].transpose(0, 1) @ gf - e[:, :m].transpose(0, 1) @ z
-    if qp.nbox:
-        yb, eb = y[:, m:], e[:, m:]
-        if "glbz" in need:
-            o["glbz"] = torch.where(yb < 0, eb, torch.zeros_like(eb)).sum(0)
-        if "gubz" in need:
-            o["gubz"] = torch.where(yb > 0, eb, torch.zeros_like(eb)).sum(0)
+    names = ("gH", "gF", "gG", "glbz", "gubz")
+    gF = "gF" in need and qp.nx > 0
+    x = keep(x0.expand(batch, qp.nx)) if gF and x0 is not None else None
+    o = _row_grads(qp, set(need) & set(names), keep(z), keep(y), keep(gf), keep(e), x)
+    o = {k: o[k] for k in names}
+    if gF and x0 is None:
+        o["gF"] = torch.zeros((qp.n, qp.nx), dtype=z.dtype, device=z.device)
     return o
 
 
@@ -203,12 +228,7 @@ def poly_loop_vjp(qp, A, B, ys, gxs=None, gus=None, gzs=None, gys=None, *, E=Non
                   gf=(T, batch, n), gw=(T, batch, nx))
     o = _alloc({**{k: (shapes[k], dt) if k in need else None for k in LOOP_VJP_OUTPUTS},
                 "vstatus": ((batch,), torch.int32)}, dev, keyed=True)
-    nbytes = loop_scratch_bytes(qp, batch, T) if gzs is not None else 0
-    if scratch is None and nbytes:
-        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    elif scratch is not None and (scratch.device.type != "cuda"
-                                  or scratch.numel() * scratch.element_size() < nbytes):
-        raise ValueError(f"scratch must be a device buffer of >= {nbytes} bytes")
+    scratch = _scratch_arg(scratch, loop_scratch_bytes(qp, batch, T) if gzs is not None else 0, dev)
     rc = batched._lib().mpcqp_mpc_poly_loop_vjp(
         batched._code(dt), batch, n, m, qp.nbox, nx, nu, T, _ptr(qp.ws), _ptr(E), _ptr(A), _ptr(B),
         _ptr(ys), _ptr(status), _ptr(gxs), _ptr(gus), _ptr(gzs), _ptr(gys),
@@ -246,7 +266,7 @@ def loop_shared_grads(qp, xs, us, zs, ys, gf, geps, gw, vstatus, need=LOOP_SHARE
             if given[u] is None:
                 raise ValueError(f"{k} needs {u}")
     ok = (vstatus == nat.STATUS_OPTIMAL)[None, :, None]
-    T, n, m, nx = int(ys.shape[0]), qp.n, qp.m, qp.nx
+    T, n, nx = int(ys.shape[0]), qp.n, qp.nx
 
     def rows(t, width):
         """(T * b, width) with the rows of failed instances zeroed"""
@@ -254,28 +274,4 @@ def loop_shared_grads(qp, xs, us, zs, ys, gf, geps, gw, vstatus, need=LOOP_SHARE
 
     x, u = rows(xs[:T], nx), rows(us, int(us.shape[-1]))
     z, y = rows(zs, n), rows(ys, qp.mt)
-    gf, e, gw = rows(gf, n), rows(geps, qp.mt), rows(gw, nx)
-    o = dict.fromkeys(LOOP_SHARED)
-    if "gH" in need:
-        S = gf.transpose(0, 1) @ z
-        St = S + S.transpose(0, 1)
-        St = St - torch.diag(torch.diagonal(S))
-        o["gH"] = batched.pack_lower(St)
-    if "gF" in need:
-        o["gF"] = gf.transpose(0, 1) @ x
-    if "gG" in need and m > 0:
-        o["gG"] = y[:, :m].transpose(0, 1) @ gf - e[:, :m].transpose(0, 1) @ z
-    if "gE" in need and m > 0:
-        o["gE"] = -(e[:, :m].transpose(0, 1) @ x)
-    if "gA" in need:
-        o["gA"] = gw.transpose(0, 1) @ x
-    if "gB" in need:
-        o["gB"] = gw.transpose(0, 1) @ u
-    if qp.nbox:
-        if "glbz" in need:
-            yb, eb = y[:, m:], e[:, m:]
-            o["glbz"] = torch.where(yb < 0, eb, torch.zeros_like(eb)).sum(0)
-        if "gubz" in need:
-            yb, eb = y[:, m:], e[:, m:]
-            o["gubz"] = torch.where(yb > 0, eb, torch.zeros_like(eb)).sum(0)
-    return o
+    return _row_grads(qp, need, z, y, rows(gf, n), rows(geps, qp.mt), x, u, rows(gw, nx))

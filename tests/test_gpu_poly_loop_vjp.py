@@ -279,6 +279,35 @@ def test_one_step_is_poly_solve_vjp(dev, which, dt):
     assert _rel(_np(r["gx0"]), _np(one["gx0"])) <= TOL[dt]
 
 
+@DT
+@pytest.mark.parametrize("shape", lc.SHAPES[:2], ids=["bs1", "bs2"])
+def test_every_step_is_poly_solve_vjp(dev, shape, dt):
+    """The loop reloads and re-sweeps W at every step: with B = 0 and gus = None
+    v = 0 at every step, so geps[t] and gf[t] of a T = 3 episode are those of
+    mpcqp_poly_solve_vjp(ys[t], gzs[t], gys[t]) bit for bit, at every t, on the
+    instances both call OPTIMAL (all of them here).  The grids are the two
+    smallest: m_total <= 8 (BS = 1) and 8 < m_total <= 16 (BS = 2)."""
+    T, batch = 3, 4
+    p = lc.shape_problem(*shape)
+    q, x0 = p["qp"], p["x0"][:batch]
+    assert (q.mt + 7) // 8 == lc.SHAPES.index(shape) + 1
+    dq = _device_qp(q, dev, dt)
+    o, (A, B, E) = _forward(q, dq, x0, T, dev, dt)
+    assert (batched.status_code(o["status"]) == OPT).all() and (o["ys"] != 0).any()
+    rng = np.random.default_rng(31)
+    gzs = _t(rng.standard_normal((T, batch, q.n)), dev, dt)
+    gys = _t(rng.standard_normal((T, batch, q.mt)), dev, dt)
+    r = poly_diff.poly_loop_vjp(dq, A, torch.zeros_like(B), o["ys"], None, None, gzs, gys, E=E,
+                                status=o["status"], need=("geps", "gf"))
+    assert r["geps"].abs().max() > 0 and r["gf"].abs().max() > 0
+    for t in range(T):
+        one = poly_diff.poly_solve_vjp(dq, o["ys"][t], gzs[t], gys[t], status=o["status"][t])
+        both = (r["vstatus"] == OPT) & (one["vstatus"] == OPT)
+        assert both.all(), (t, r["vstatus"], one["vstatus"])
+        for k, got, ref in (("geps", r["geps"][t], one["e"]), ("gf", r["gf"][t], one["gf"])):
+            assert torch.equal(_bits(got[both]), _bits(ref[both])), (t, k)
+
+
 # ------------------------------------------------------------------ (c)
 def test_box_only_vs_box_loop_adjoint(dev):
     """m = 0: the same episode through mpcqp_mpc_box_loop (whose z holds active
